@@ -9,6 +9,18 @@ second (GiB/s, 2^30), per-GPU work fixed (weak scaling: every rank owns its
 own disjoint page range, no collective on the data path).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1|2|3|4|5|6|7]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: it generates the batch, runs
+untimed steps until the part is in its steady state (--settle-ms), W warmup
+steps, times K steps, and prints one JSON line (metric, value, unit,
+ms_per_step = wall milliseconds per timed step, the roofline of the timed
+launches).  --dump-outputs DIR then writes what the last timed step computed
+as DIR/<name>.npy (see timed_outputs()); the pages are generated from a fixed
+seed, so two builds run with the same arguments can be compared array for
+array.  Everything listed under "--full" below (measurements and checks that
+take runs of their own) is run, and reported on the same line, only with
+--full.
 
 Workload: N=1 defaults to BASELINE config 2 (1,048,576 x 4 KiB pages, 4 GiB);
 N>1 (torch.distributed.run, one process per GPU) defaults to BASELINE config 5
@@ -17,9 +29,10 @@ control plane (barrier + max over ranks of the timed region).  Configs 6/7 are
 the north star's 8/16 KiB page-size sweep (4 GiB per GPU).  --config 1 runs
 only the CPU reference over the 1 GiB file (BASELINE configs[0]).
 
-Also reported, on the same line:
+With --full, also reported on the same line:
   roofline      dominant kernel's algorithmic bytes per launch / average launch
-                time (HIP events on the launch stream) vs 8 TB/s HBM peak;
+                time (HIP events on the launch stream) vs 8 TB/s HBM peak (a
+                plain run reports this much, with the committed traffic);
                 traffic = PMC-measured HBM bytes per launch: at the default
                 config, two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE)
                 over the headline kernel in this run (traffic_live); else, or
@@ -1021,6 +1034,60 @@ def live_traffic(timeout_s: int = 90):
                       "(read = FETCH_SIZE*1024*2, write = WRITE_SIZE*1024, median over dispatches)"}
 
 
+DUMP_MAX_ROWS = 1 << 21  # per array: 32 MiB of (lo, hi) float64 pairs; larger outputs are sampled
+DUMP_SAMPLE_SEED = 0xD0C5
+
+
+def u64_halves(x: torch.Tensor) -> np.ndarray:
+    """64-bit words as an exact float64 array of shape (n, 2): column 0 the
+    low 32 bits, column 1 the high 32 bits (float64 holds 53 bits)."""
+    u = x.cpu().numpy().view(np.uint64).ravel()
+    return np.stack([(u & np.uint64(0xFFFFFFFF)).astype(np.float64), (u >> np.uint64(32)).astype(np.float64)], axis=1)
+
+
+def timed_outputs(w: Workload, mode: str) -> dict:
+    """What the last timed step left for its caller, per mode:
+      digest    digests      the per-page digests (w.out)
+      validate  ok           the per-page verdicts, 0/1 as float32
+                first_bad    index of the first failing page (n if none)
+      stamp     headers      the 8-byte header the step wrote into each page
+    64-bit words are stored as (low 32 bits, high 32 bits) float64 pairs
+    (u64_halves).  An output of more than DUMP_MAX_ROWS pages is sampled: a
+    fixed, seeded, sorted choice of DUMP_MAX_ROWS page indices, the same in
+    every run, stored beside it as sample_index."""
+    idx = None
+    if w.n > DUMP_MAX_ROWS:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(w.n, DUMP_MAX_ROWS, replace=False))
+    tidx = torch.from_numpy(idx).to(w.dev) if idx is not None else None
+
+    def rows(t: torch.Tensor) -> torch.Tensor:
+        return t if tidx is None else t.index_select(0, tidx)
+
+    if mode == "digest":
+        out = {"digests": u64_halves(rows(w.out))}
+    elif mode == "validate":
+        out = {"ok": rows(w.ok).cpu().numpy().astype(np.float32),
+               "first_bad": w.fb.cpu().numpy().astype(np.float64)}
+    else:
+        if w.P is not None:
+            hdr = rows(w.pages.view(w.n, w.P)[:, :8]).contiguous()
+        else:
+            at = rows(w.d_off)[:, None] + torch.arange(8, device=w.dev)
+            hdr = w.pages[at]
+        out = {"headers": u64_halves(hdr.view(torch.int64))}
+    if idx is not None:
+        out["sample_index"] = idx.astype(np.float64)
+    return out
+
+
+def dump_outputs(d: str, arrays: dict, rank: int | None = None) -> None:
+    """DIR/<name>.npy for every array (DIR/<name>_rank<r>.npy at N > 1)."""
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(d, name + ("" if rank is None else f"_rank{rank}") + ".npy"), a)
+
+
 def guarded_check(fn, *a, **kw):
     """A parity sample or drill that raises becomes a failing record
     ({"error", "pass": False}) instead of an exception."""
@@ -1070,6 +1137,12 @@ def main():
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="take roofline.traffic from the committed profiles/ summary instead of two rocprofv3 "
                          "--pmc passes in this run")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the cold protocol, parity and the corruption "
+                         "drill, the streaming-read ceiling, the host-inclusive legs, the sweep, the CPU baselines "
+                         "(config 1), live PMC traffic, and at N>1 the solo run and the multi-rank sweep")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--settle-ms", type=float, default=SETTLE_MS,
                     help="untimed steps for at least this long before the W warmup steps (0: none)")
@@ -1122,8 +1195,10 @@ def main():
     time.sleep(PHASE_GAP_S)
     # The driver's own protocol first, with no settle: W
     # warmup steps, then K timed steps, on the part as the process finds it.
-    cold = cold_rate(dist, w, args.mode, min(args.steps, 400), args.warmup)
-    time.sleep(PHASE_GAP_S)
+    cold = None
+    if args.full:
+        cold = cold_rate(dist, w, args.mode, min(args.steps, 400), args.warmup)
+        time.sleep(PHASE_GAP_S)
     settle_steps = settle(w, args.mode, args.settle_ms)
     for _ in range(args.warmup):
         w.step(args.mode)
@@ -1154,9 +1229,11 @@ def main():
     total_bytes = sum_over_ranks(dist, float(w.bytes)) * args.steps
     value = total_bytes / elapsed / GIB
     time.sleep(PHASE_GAP_S)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, timed_outputs(w, args.mode), rank if dist is not None else None)
 
     scaling = None
-    if dist is not None:
+    if dist is not None and args.full:
         # Per-rank evidence, then rank 0 alone on its own shard (the others wait
         # at the barrier): concurrent per-GPU rate / solo rate, an interference
         # check (the driver computes scaling efficiency from the per-N lines).
@@ -1182,7 +1259,7 @@ def main():
                        "shared_gpus": ndev < world}
         time.sleep(PHASE_GAP_S)
 
-    if args.mode != "digest":  # leave self.out holding this batch's digests for the parity leg
+    if args.full and args.mode != "digest":  # leave self.out holding this batch's digests for the parity leg
         w.step("digest")
         torch.cuda.synchronize()
     # Parity and the corruption drill on EVERY rank, each over its own shard
@@ -1190,12 +1267,15 @@ def main():
     # carries them all and the run fails if any rank's does.
     # Each guarded per rank: a rank whose check raises records
     # it as failed and still reaches the gather, so no rank waits forever.
-    parity = guarded_check(parity_sample, w)
-    ceiling = guarded("ceiling", w.ceiling_ab) if args.mode == "digest" and w.P == 4096 else None
-    time.sleep(PHASE_GAP_S)
-    drill = guarded_check(w.corruption_drill)
-    time.sleep(PHASE_GAP_S)
-    per_rank_checks, checks_ok = gather_checks(dist, world, rank, parity, drill)
+    parity = drill = ceiling = None
+    per_rank_checks, checks_ok = [], True
+    if args.full:
+        parity = guarded_check(parity_sample, w)
+        ceiling = guarded("ceiling", w.ceiling_ab) if args.mode == "digest" and w.P == 4096 else None
+        time.sleep(PHASE_GAP_S)
+        drill = guarded_check(w.corruption_drill)
+        time.sleep(PHASE_GAP_S)
+        per_rank_checks, checks_ok = gather_checks(dist, world, rank, parity, drill)
     # Optional legs, each guarded: a failure is recorded under its key and the
     # headline line (roofline, parity, drill) still prints.  The sweep runs
     # before config 1: with config 1 first (its CLI processes initialise the
@@ -1204,21 +1284,21 @@ def main():
     # the wall budget are skipped, and config 1 is skipped when the time left
     # cannot hold it.
     hostinc = None
-    if not args.no_host_inclusive and rank == 0 and world == 1:
+    if args.full and not args.no_host_inclusive and rank == 0 and world == 1:
         hostinc = guarded("host_inclusive", host_inclusive, w) if time.perf_counter() < deadline else \
             {"skipped": "bench wall budget spent"}
     multi_entries = None
-    if world > 1 and not args.no_sweep:
+    if args.full and world > 1 and not args.no_sweep:
         multi_entries = multi_rank_sweep(dist, world, rank, dev, algo, args.sweep_steps, args.sweep_warmup,
                                          max(1, args.sweep_scale), min(args.settle_ms, SWEEP_SETTLE_MS), deadline)
         checks_ok = checks_ok and all(e.get("checks_all_ranks_pass") for e in multi_entries if "skipped" not in e)
     sweep_entries = None
-    if rank == 0 and world == 1 and not args.no_sweep:
+    if args.full and rank == 0 and world == 1 and not args.no_sweep:
         sweep_entries = guarded("sweep", sweep, dev, args.sweep_steps, args.sweep_warmup,
                                 head=w if algo == 0 else None, scale=max(1, args.sweep_scale), deadline=deadline,
                                 settle_ms=min(args.settle_ms, SWEEP_SETTLE_MS))
     c1 = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         all_s = None if args.no_all_cores else min(args.cpu_seconds, 5.0)
         need = args.cpu_seconds + 2 * (all_s or 0) + 3.0 + 30.0  # + port leg + gen/scan/warm margin
         if time.perf_counter() + need > deadline:
@@ -1227,7 +1307,7 @@ def main():
             c1 = guarded("config1", config1, args.cpu_seconds, all_s)
 
     live = None
-    if (rank == 0 and world == 1 and cfg == 2 and algo == pcs.XXH3_64 and args.mode == "digest"
+    if (args.full and rank == 0 and world == 1 and cfg == 2 and algo == pcs.XXH3_64 and args.mode == "digest"
             and args.pages_per_gpu is None and not args.no_live_traffic):
         live = guarded("live_traffic", live_traffic) if time.perf_counter() + 60 < deadline else \
             {"skipped": "bench wall budget spent"}
@@ -1281,17 +1361,21 @@ def main():
                 "avg_launch_ms": round(avg_launch * 1e3, 4),
                 "launch_timing": f"HIP events bracketing the {args.steps} timed steps on the launch stream",
             },
-            "stream_read_GBps": ceiling.get("stream_read_GBps") if ceiling else None,
-            "ceiling": ceiling,
-            "cold": cold,
-            "cpu_baseline": c1.get("cpu_baseline") if c1 else None,
-            "parity": parity,
         }
-        line["corruption_drill"] = drill
-        if world > 1:
-            line["parity_per_rank"] = [dict(c["parity"], rank=c["rank"]) for c in per_rank_checks]
-            line["drill_per_rank"] = [dict(c["corruption_drill"], rank=c["rank"]) for c in per_rank_checks]
-        line["checks_all_ranks_pass"] = checks_ok
+        if args.full:
+            line["stream_read_GBps"] = ceiling.get("stream_read_GBps") if ceiling else None
+            line["ceiling"] = ceiling
+            line["cold"] = cold
+            line["cpu_baseline"] = c1.get("cpu_baseline") if c1 else None
+            line["parity"] = parity
+            line["corruption_drill"] = drill
+            if world > 1:
+                line["parity_per_rank"] = [dict(c["parity"], rank=c["rank"]) for c in per_rank_checks]
+                line["drill_per_rank"] = [dict(c["corruption_drill"], rank=c["rank"]) for c in per_rank_checks]
+            line["checks_all_ranks_pass"] = checks_ok
+        line["full"] = args.full
+        if args.dump_outputs:
+            line["dump_outputs"] = args.dump_outputs
         if c1 is not None:
             for k in ("cpu_all_cores", "cpu_port", "cpu_ref_inmem", "cpu_ref_inmem_all_cores", "cli_scan"):
                 line[k] = c1.get(k)

@@ -89,3 +89,17 @@ def test_settle_runs_whole_batches_for_at_least_the_time(monkeypatch):
     n = bench.settle(FakeWorkload(), "digest", 30)
     assert time.perf_counter() - t0 >= 0.030
     assert n == calls["step"] and n % 8 == 0 and n >= 8 and calls["sync"] == n // 8
+
+
+def test_u64_halves_are_exact():
+    """--dump-outputs stores 64-bit words as (low 32, high 32) float64 pairs,
+    which reassemble bit for bit."""
+    import numpy as np
+    import torch
+
+    u = np.array([0, 1, 0xFFFFFFFF, 1 << 32, 0xFFFFFFFFFFFFFFFF, 0x0123456789ABCDEF], dtype=np.uint64)
+    h = bench.u64_halves(torch.from_numpy(u.view(np.int64)))
+    assert h.dtype == np.float64 and h.shape == (6, 2)
+    assert np.array_equal(h[:, 0].astype(np.uint64) | (h[:, 1].astype(np.uint64) << np.uint64(32)), u)
+    # two 32 MiB arrays at the most (values + their sample index): under 64 MB in all
+    assert bench.DUMP_MAX_ROWS * (16 + 8) <= 64 * 10**6

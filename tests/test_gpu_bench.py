@@ -1,13 +1,16 @@
 """bench.py's N = 1 line carries what the driver and the judge read: the
-headline metric with its roofline, parity and corruption drill, and the sweep
-over every other BASELINE config and mode, each entry with
-its launch time, frac, parity against the reference build and a drill.  Run
-at reduced sizes (--pages-per-gpu, --sweep-scale) so it takes seconds."""
+headline metric with its roofline and ms_per_step in a plain run (which can
+dump the last timed step's outputs); with --full also parity and the
+corruption drill, and the sweep over every other BASELINE config and mode
+(VERDICT r01 #2), each entry with its launch time, frac, parity against the
+reference build and a drill.  Run at reduced sizes (--pages-per-gpu,
+--sweep-scale) so it takes seconds."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -18,7 +21,7 @@ SWEEP_KEYS = ["config3_xxh3", "config3_xxh64", "config4_xxh3", "config5_xxh3", "
 
 
 def test_bench_line_and_sweep():
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "5", "--warmup", "2", "--pages-per-gpu", "65536",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "5", "--warmup", "2", "--pages-per-gpu", "65536",
                         "--sweep-steps", "3", "--sweep-warmup", "1", "--sweep-scale", "16", "--no-cpu-baseline",
                         "--no-host-inclusive"],
                        cwd=ROOT, capture_output=True, text=True, timeout=300)
@@ -84,7 +87,7 @@ def test_config1_leg_on_the_real_file():
 
 def test_bench_line_survives_failing_config1():
     env = dict(os.environ, PCS_BENCH_FAIL_CONFIG1="1")
-    d = _one_line(subprocess.run([sys.executable, "bench.py", "--steps", "5", "--warmup", "2", "--pages-per-gpu",
+    d = _one_line(subprocess.run([sys.executable, "bench.py", "--full", "--steps", "5", "--warmup", "2", "--pages-per-gpu",
                                   "65536", "--no-sweep", "--host-inclusive"], cwd=ROOT, env=env,
                                  capture_output=True, text=True, timeout=300))
     assert "PCS_BENCH_FAIL_CONFIG1" in d["config1_error"]
@@ -98,15 +101,15 @@ def test_bench_line_survives_failing_config1():
 
 
 def test_host_inclusive_runs_by_default():
-    """VERDICT r05 #3: the N=1 line carries the host-inclusive legs by default."""
-    d = _one_line(subprocess.run([sys.executable, "bench.py", "--steps", "5", "--warmup", "2", "--pages-per-gpu",
+    """VERDICT r05 #3: the N=1 --full line carries the host-inclusive legs without being asked for them."""
+    d = _one_line(subprocess.run([sys.executable, "bench.py", "--full", "--steps", "5", "--warmup", "2", "--pages-per-gpu",
                                   "65536", "--no-sweep", "--no-cpu-baseline", "--no-live-traffic"], cwd=ROOT,
                                  capture_output=True, text=True, timeout=300))
     assert d["host_inclusive"]["parity_mismatches"] == 0 and d["host_inclusive"]["pages"] == 65536
 
 
 def test_bench_wall_budget_skips_optional_legs():
-    d = _one_line(subprocess.run([sys.executable, "bench.py", "--steps", "5", "--warmup", "2", "--pages-per-gpu",
+    d = _one_line(subprocess.run([sys.executable, "bench.py", "--full", "--steps", "5", "--warmup", "2", "--pages-per-gpu",
                                   "65536", "--sweep-scale", "16", "--wall-budget", "0"], cwd=ROOT,
                                  capture_output=True, text=True, timeout=300))
     assert "wall budget" in d["config1_skipped"]
@@ -119,7 +122,7 @@ def test_live_traffic_leg():
     rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) over the headline kernel in
     this very run, corrected for gfx950; on this streaming kernel it equals
     the algorithmic bytes (VERDICT r03 weak #9)."""
-    d = _one_line(subprocess.run([sys.executable, "bench.py", "--steps", "5", "--warmup", "2", "--no-sweep",
+    d = _one_line(subprocess.run([sys.executable, "bench.py", "--full", "--steps", "5", "--warmup", "2", "--no-sweep",
                                   "--no-cpu-baseline"], cwd=ROOT, capture_output=True, text=True, timeout=300))
     roof = d["roofline"]
     live = roof["traffic_live"]
@@ -127,3 +130,74 @@ def test_live_traffic_leg():
     assert roof["traffic_source"].startswith("live:") and roof["traffic"] == live["traffic"]
     assert 0.98 < roof["traffic"] / roof["algorithmic_bytes_per_launch"] < 1.05, roof
     assert live["dispatches"]["FETCH_SIZE"] >= 3 and live["dispatches"]["WRITE_SIZE"] >= 3
+
+
+FULL_ONLY = ("cold", "parity", "corruption_drill", "ceiling", "stream_read_GBps", "cpu_baseline", "host_inclusive",
+             "sweep", "checks_all_ranks_pass")
+
+
+def _u64(halves):
+    assert halves.dtype == np.float64 and halves.ndim == 2 and halves.shape[1] == 2
+    return halves[:, 0].astype(np.uint64) | (halves[:, 1].astype(np.uint64) << np.uint64(32))
+
+
+def test_plain_run_is_the_headline_only_and_dumps_its_digests(tmp_path):
+    """Without --full: W warmup and K timed steps, one line with the headline
+    fields and ms_per_step, none of the legs that take runs of their own; and
+    --dump-outputs writes the last timed step's digests (low and high 32 bits
+    as exact float64 pairs), which are the oracle's digests of the generator's
+    pages for this seed."""
+    import oracle
+    from workload import fill_pages
+
+    n = 4097
+    d = _one_line(subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1",
+                                  "--pages-per-gpu", str(n), "--dump-outputs", str(tmp_path / "out")], cwd=ROOT,
+                                 capture_output=True, text=True, timeout=120))
+    assert d["metric"] == "GiB/s device-resident batched page XXH3-64, 4 KiB pages, 1/2/4/8 MI355X"
+    assert d["unit"] == "GiB/s" and d["higher_is_better"] is True and d["dtype"] == "u64" and d["full"] is False
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    # value = bytes per step / the wall time of one step
+    assert abs(d["value"] - n * 4096 / (d["ms_per_step"] / 1e3) / 2**30) <= 0.02 * d["value"]
+    assert d["roofline"]["frac"] > 0 and d["roofline"]["avg_launch_ms"] > 0
+    assert not [k for k in FULL_ONLY if k in d], d.keys()
+    assert os.listdir(tmp_path / "out") == ["digests.npy"]
+    got = _u64(np.load(tmp_path / "out" / "digests.npy"))
+    assert np.array_equal(got, oracle.pages_digest(fill_pages(0x5EED0002, 0, n, 4096).reshape(-1), 4096))
+
+
+def test_timed_outputs_of_every_mode(tmp_path, monkeypatch):
+    """bench.timed_outputs: validate leaves verdicts and the first bad index,
+    stamp the headers it wrote (fixed and mixed page sizes), all float32 or
+    float64; bench.dump_outputs writes one .npy per array."""
+    import bench
+    import oracle
+
+    w = bench.Workload(2, 0, 0, 1000, "cuda:0")
+    w.step("stamp")
+    hdr = bench.timed_outputs(w, "stamp")
+    want = oracle.pages_digest(w.pages.cpu().numpy(), 4096)
+    assert list(hdr) == ["headers"] and np.array_equal(_u64(hdr["headers"]), want)
+    w.pages[3 * 4096 + 10] ^= 0xFF
+    w.step("validate")
+    out = bench.timed_outputs(w, "validate")
+    assert out["ok"].dtype == np.float32 and out["ok"].shape == (1000,)
+    assert out["ok"].sum() == 999 and out["ok"][3] == 0 and out["first_bad"].tolist() == [3.0]
+    m = bench.Workload(3, 0, 0, 300, "cuda:0")
+    m.step("stamp")
+    got = _u64(bench.timed_outputs(m, "stamp")["headers"])
+    assert np.array_equal(got, oracle.desc_digest(m.pages.cpu().numpy(), m.offs, m.lens))
+    # an output larger than DUMP_MAX_ROWS: the same seeded, sorted sample of rows in every call
+    monkeypatch.setattr(bench, "DUMP_MAX_ROWS", 256)
+    a, b = bench.timed_outputs(w, "stamp"), bench.timed_outputs(m, "stamp")
+    idx = a["sample_index"].astype(np.int64)
+    assert len(np.unique(idx)) == 256 and (np.diff(idx) > 0).all() and idx.max() < 1000
+    assert np.array_equal(_u64(a["headers"]), _u64(hdr["headers"])[idx])
+    assert np.array_equal(_u64(b["headers"]), got[b["sample_index"].astype(np.int64)])
+    w.step("digest")
+    d = bench.timed_outputs(w, "digest")
+    assert np.array_equal(d["sample_index"], a["sample_index"])
+    assert np.array_equal(_u64(d["digests"]), w.out.cpu().numpy().view(np.uint64)[idx])
+    bench.dump_outputs(str(tmp_path / "o"), out, rank=1)
+    assert sorted(os.listdir(tmp_path / "o")) == ["first_bad_rank1.npy", "ok_rank1.npy"]
+    assert np.array_equal(np.load(tmp_path / "o" / "ok_rank1.npy"), out["ok"])

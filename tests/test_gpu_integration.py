@@ -1,6 +1,7 @@
 """Runs INTEGRATION.md's call-site snippets on the GPU (built by
-tests/cpp/gen_integration.py in the build container, where the reference's
-page.h exists; the binary travels with the tree).
+__graft_entry__.build() through tests/cpp/gen_integration.py: against the
+reference's page.h where the reference tree exists, else against the stand-in
+header tests/cpp/standin/storage/page.h, so any checkout builds the binary).
 
 The binary drives the ReadPages validate loop (sync and async, registered pool
 and heap pages, a corrupted page at index 77, skip_verify_checksum), and the
@@ -29,7 +30,7 @@ pytestmark = pytest.mark.gpu
 
 
 def test_integration_snippets_run():
-    assert os.path.exists(BIN), "tests/cpp/integration_snippets missing: run __graft_entry__.build() with the reference tree present"
+    assert os.path.exists(BIN), "tests/cpp/integration_snippets missing: run __graft_entry__.build()"
     r = subprocess.run([BIN], capture_output=True, text=True, timeout=100)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "integration ok" in r.stdout

@@ -82,7 +82,7 @@ def test_bench_two_ranks_torchrun():
     wall/kernel-event times and the concurrent rate against its solo rate."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
-           "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1"]
+           "bench.py", "--full", "--gpus", "2", "--steps", "3", "--warmup", "1"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -124,7 +124,7 @@ def test_bench_four_ranks_torchrun():
     line, each over its own global range."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
-           "bench.py", "--gpus", "4", "--steps", "3", "--warmup", "1", "--pages-per-gpu", str(1 << 20),
+           "bench.py", "--full", "--gpus", "4", "--steps", "3", "--warmup", "1", "--pages-per-gpu", str(1 << 20),
            "--sweep-steps", "3", "--sweep-warmup", "1", "--sweep-scale", "16"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -122,3 +122,25 @@ def test_c_blocks_compile(name, body, tmp_path):
 
 def test_doc_has_a_c_block():
     assert _C_BLOCK.findall(open(DOC).read())
+
+
+def test_snippets_compile_against_the_standin_page_h(monkeypatch, tmp_path):
+    """A checkout without the reference tree builds the call-site snippets
+    against tests/cpp/standin/storage/page.h, and without oracle/_ref hashes
+    with the oracle (tests/cpp/gen_integration.py): both must keep compiling,
+    or tests/test_gpu_integration.py loses its binary there."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests", "cpp"))
+    import gen_integration as gi
+
+    monkeypatch.setattr(gi, "REF", str(tmp_path / "no_reference"))
+    assert not gi.reference_present()
+    r = gi.compile_tu(str(tmp_path / "x"), syntax_only=True)
+    assert r.returncode == 0, r.stderr
+    if os.path.exists(os.path.join(ROOT, "eloqstore_amd", "libeloqstore_pcs.so")):
+        monkeypatch.setattr(gi, "REF_SO", str(tmp_path / "no_ref_so"))
+        out = tmp_path / "integration_snippets"
+        r = gi.compile_tu(str(out), syntax_only=False)
+        assert r.returncode == 0, r.stderr
+        undefined = subprocess.run(["nm", "-D", "--undefined-only", str(out)], capture_output=True, text=True).stdout
+        assert "oracle_xxh3_64" in undefined and "XXH3_64bits" not in undefined

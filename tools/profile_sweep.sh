@@ -1,7 +1,7 @@
 #!/bin/bash
 # tools/profile_sweep.sh <tag> — rocprofv3 evidence for every bench entry.
 # Run on the GPU box from the repo root.  Writes gpurun_out/prof_<tag>/:
-#   trace/  kernel trace + stats of the default N=1 bench run (headline + sweep)
+#   trace/  kernel trace + stats of the N=1 bench run with --full (headline + sweep)
 #   fetch/  --pmc FETCH_SIZE over a short run of the same entries
 #   write/  --pmc WRITE_SIZE over a short run (separate pass: gfx950 PMC slots)
 #   utcl/   --pmc UTCL1 address-translation counters (requests, hits, misses,
@@ -16,8 +16,8 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 # (host-inclusive legs off: PCIe-bound, measured in the bench line itself)
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o bench --output-format csv -- \
-    python3 bench.py --no-cpu-baseline --no-live-traffic --no-host-inclusive > "$OUT/bench_trace.json" 2> "$OUT/bench_trace.err"
-SHORT="--steps 5 --warmup 2 --sweep-steps 5 --sweep-warmup 1 --no-cpu-baseline --no-live-traffic --no-host-inclusive"
+    python3 bench.py --full --no-cpu-baseline --no-live-traffic --no-host-inclusive > "$OUT/bench_trace.json" 2> "$OUT/bench_trace.err"
+SHORT="--full --steps 5 --warmup 2 --sweep-steps 5 --sweep-warmup 1 --no-cpu-baseline --no-live-traffic --no-host-inclusive"
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -d "$OUT/fetch" -o fetch --output-format csv -- \
     python3 bench.py $SHORT > "$OUT/bench_fetch.json" 2> "$OUT/bench_fetch.err"
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE -d "$OUT/write" -o write --output-format csv -- \
