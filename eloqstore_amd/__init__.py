@@ -47,6 +47,8 @@ _SIGS = {
     "pcs_pages_digest_dev": [_vp, _u64, _u64, _i32, _vp, _vp],
     "pcs_pages_validate_dev": [_vp, _u64, _u64, _i32, _vp, _vp, _vp],
     "pcs_pages_stamp_dev": [_vp, _u64, _u64, _i32, _vp],
+    "pcs_pages_scrub_dev": [_vp, _u64, _u64, _vp, _vp, _vp, _vp, _u64, _vp],
+    "pcs_pages_scrub_host": [_vp, _u64, _u64, _vp, _vp, _vp, _vp, _u64],
     "pcs_desc_digest_dev": [_vp, _vp, _vp, _u64, _i32, _vp, _vp],
     "pcs_desc_validate_dev": [_vp, _vp, _vp, _u64, _i32, _vp, _vp, _vp],
     "pcs_desc_stamp_dev": [_vp, _vp, _vp, _u64, _i32, _vp],
@@ -205,7 +207,7 @@ def version() -> str:
     return lib().pcs_version().decode()
 
 
-ABI_VERSION = 6  # PCS_ABI_VERSION of include/eloqstore_pcs.h this binding was written for
+ABI_VERSION = 7  # PCS_ABI_VERSION of include/eloqstore_pcs.h this binding was written for
 
 
 def abi_version() -> int:
@@ -245,6 +247,50 @@ def pages_validate(pages, page_size: int, n: int, algo: int = XXH3_64, ok=None, 
 
 def pages_stamp(pages, page_size: int, n: int, algo: int = XXH3_64, stream=None) -> None:
     _call("pcs_pages_stamp_dev", _ptr(pages), page_size, n, algo, _stream(stream))
+
+
+PAGE_CORRUPT, PAGE_OK, PAGE_BLANK = 0, 1, 2  # pcs_page_class
+_SUMMARY_WORDS = 12  # pcs_scrub_summary
+TYPE_BUCKETS = ("nonleaf_index", "leaf_index", "data", "overflow", "deleted", "other")
+NO_PAGE = (1 << 64) - 1  # first_corrupt when no page is corrupt
+
+
+def summary_dict(words) -> dict:
+    """pcs_scrub_summary (12 u64 words) as a dict."""
+    w = [int(x) & NO_PAGE for x in words]
+    return {"n_pages": w[0], "n_ok": w[1], "n_corrupt": w[2], "n_blank": w[3], "ok_by_type": w[4:10],
+            "first_corrupt": w[10], "n_listed": w[11]}
+
+
+def pages_scrub_async(pages, page_size: int, n: int, cls=None, types=None, summary=None, corrupt=None,
+                      corrupt_cap: int = 1024, stream=None):
+    """pcs_pages_scrub_dev, enqueue only: returns the device tensors (cls,
+    types, summary words, corrupt list), valid once the stream is synchronised.
+    types=False passes a NULL type array; cap 0 passes a NULL list."""
+    if cls is None:
+        cls = torch.empty(n, dtype=torch.uint8, device=pages.device)
+    if types is None:
+        types = torch.empty(n, dtype=torch.uint8, device=pages.device)
+    if summary is None:
+        summary = torch.empty(_SUMMARY_WORDS, dtype=torch.int64, device=pages.device)
+    if corrupt is None and corrupt_cap:
+        corrupt = torch.empty(corrupt_cap, dtype=torch.int64, device=pages.device)
+    _call("pcs_pages_scrub_dev", _ptr(pages), page_size, n, _ptr(cls), _ptr(None if types is False else types),
+          _ptr(summary), _ptr(corrupt) if corrupt_cap else 0, corrupt_cap, _stream(stream))
+    return cls, (None if types is False else types), summary, corrupt
+
+
+def pages_scrub(pages, page_size: int, n: int, cls=None, types=None, corrupt_cap: int = 1024, stream=None):
+    """Classify n device pages (PAGE_OK / PAGE_BLANK / PAGE_CORRUPT), report
+    their type bytes, count them and list the smallest corrupt page indices:
+    -> (cls, types, summary dict, corrupt tensor of n_listed indices).  Waits
+    for the stream (the summary is read on the host)."""
+    cls, types, summary, corrupt = pages_scrub_async(pages, page_size, n, cls, types, None, None, corrupt_cap, stream)
+    if stream is not None:  # the copy below is ordered on torch's current stream only
+        _call("pcs_synchronize", _stream(stream))
+    d = summary_dict(summary.cpu().tolist())
+    listed = corrupt[: d["n_listed"]] if corrupt is not None else torch.empty(0, dtype=torch.int64, device=pages.device)
+    return cls, types, d, listed
 
 
 def desc_digest(base, off, length, n: int, algo: int = XXH3_64, out=None, stream=None):
@@ -461,6 +507,28 @@ def digest_ptrs(ptrs, page_size: int, algo: int = XXH3_64) -> np.ndarray:
     out = np.zeros(max(1, len(ptrs)), dtype=np.uint64)
     _call("pcs_pages_digest_host", ptrs.ctypes.data, page_size, len(ptrs), algo, out.ctypes.data)
     return out[: len(ptrs)]
+
+
+def scrub_ptrs(ptrs, page_size: int, corrupt_cap: int = 1024):
+    """pcs_pages_scrub_host over raw host page addresses ->
+    (cls array, types array, summary dict, corrupt index array)."""
+    ptrs = np.ascontiguousarray(ptrs, dtype=np.uint64)
+    n = len(ptrs)
+    cls = np.zeros(max(1, n), dtype=np.uint8)
+    types = np.zeros(max(1, n), dtype=np.uint8)
+    summary = np.zeros(_SUMMARY_WORDS, dtype=np.uint64)
+    corrupt = np.zeros(max(1, corrupt_cap), dtype=np.uint64)
+    _call("pcs_pages_scrub_host", ptrs.ctypes.data, page_size, n, cls.ctypes.data, types.ctypes.data,
+          summary.ctypes.data, corrupt.ctypes.data if corrupt_cap else 0, corrupt_cap)
+    d = summary_dict(summary)
+    return cls[:n], types[:n], d, corrupt[: d["n_listed"]]
+
+
+def scrub_pages_host(pages: list, page_size: int, corrupt_cap: int = 1024):
+    """Scrub scattered host buffers (bytearrays): see scrub_ptrs."""
+    arr, _keep = _page_ptrs(pages)
+    ptrs = np.array([arr[i] or 0 for i in range(len(pages))], dtype=np.uint64)
+    return scrub_ptrs(ptrs, page_size, corrupt_cap)
 
 
 class ValidateService:

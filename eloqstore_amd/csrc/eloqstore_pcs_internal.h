@@ -14,6 +14,14 @@ namespace pcs {
 hipError_t run_pages(int mode, int algo, const uint8_t* pages, uint64_t page_size, uint64_t n, uint64_t* out,
                      uint8_t* ok, unsigned long long* first_bad, hipStream_t s);
 
+// Scrub of fixed-stride XXH3 pages (249 <= page_size < 2^32, any alignment):
+// cls[i] = pcs_page_class, type[i] = page byte 8 (type may be null: scratch
+// is leased for it), summary = the 12 words of pcs_scrub_summary, list[0 ..
+// min(n_corrupt, cap)) = the smallest corrupt page indices, ascending.  All
+// device memory; enqueues on s and never waits.
+hipError_t run_scrub(const uint8_t* pages, uint64_t page_size, uint64_t n, uint8_t* cls, uint8_t* type,
+                     uint64_t* summary, uint64_t* list, uint64_t cap, hipStream_t s);
+
 // Descriptor batch: range i = [base + off[i], +len[i]).  skip = 8 applies the
 // page convention (digest over [8, len), stored digest at [0, 8)); skip = 0
 // hashes the raw range.  seed is used by XXH64 only (XXH3 path is seed 0).

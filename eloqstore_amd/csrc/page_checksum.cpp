@@ -4,6 +4,7 @@
 // of their own, so linking this one never interposes on page.cpp's.
 #include "eloqstore/page_checksum.h"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -54,6 +55,32 @@ void PageDigests(std::span<const char* const> pages, size_t page_size, uint64_t*
     if (int rc = pcs_pages_digest_host(reinterpret_cast<const void* const*>(pages.data()), page_size, pages.size(),
                                        static_cast<int>(hash), digests_out))
         die("PageDigests", rc);
+}
+
+int TryScrubPages(std::span<const char* const> pages, size_t page_size, ScrubReport& report, size_t max_listed) {
+    const size_t n = pages.size();
+    report.page_class.assign(n, 0);
+    report.page_type.assign(n, 0);
+    report.corrupt.assign(std::min(max_listed, n), 0);
+    pcs_scrub_summary sum{};
+    const int rc = pcs_pages_scrub_host(reinterpret_cast<const void* const*>(pages.data()), page_size, n,
+                                        report.page_class.data(), report.page_type.data(), &sum,
+                                        report.corrupt.data(), report.corrupt.size());
+    if (rc != PCS_OK) return rc;
+    report.n_pages = sum.n_pages;
+    report.n_ok = sum.n_ok;
+    report.n_corrupt = sum.n_corrupt;
+    report.n_blank = sum.n_blank;
+    for (int k = 0; k < 6; ++k) report.ok_by_type[k] = sum.ok_by_type[k];
+    report.first_corrupt = sum.first_corrupt;
+    report.corrupt.resize(sum.n_listed);
+    return PCS_OK;
+}
+
+ScrubReport ScrubPages(std::span<const char* const> pages, size_t page_size, size_t max_listed) {
+    ScrubReport report;
+    if (int rc = TryScrubPages(pages, page_size, report, max_listed)) die("ScrubPages", rc);
+    return report;
 }
 
 void RegisterPagePool(void* base, size_t bytes) {

@@ -7,6 +7,7 @@
 #include "eloqstore_pcs.h"
 #include "eloqstore_pcs_internal.h"
 #include "region_registry.h"
+#include "scrub_merge.h"
 
 #include <hip/hip_runtime.h>
 
@@ -273,6 +274,15 @@ struct Slot {
     size_t cap_pages_bytes = 0, cap_dev_bytes = 0, cap_n = 0;
     uint64_t first = 0, count = 0;  // chunk currently in flight
     bool busy = false;
+    // scrub only (ensure_scrub_slot): type bytes, the chunk's summary and its corrupt list
+    uint8_t* h_type = nullptr;   // pinned
+    uint8_t* d_type = nullptr;
+    pcs_scrub_summary* h_sum = nullptr;  // pinned
+    pcs_scrub_summary* d_sum = nullptr;
+    uint64_t* h_list = nullptr;  // pinned
+    uint64_t* d_list = nullptr;
+    size_t cap_type = 0, cap_list = 0;
+    uint64_t listed = 0;  // list entries asked of the chunk in flight
 };
 
 constexpr int kSlots = 3;  // H2D of chunk k+1 || kernel k || D2H k-1
@@ -291,6 +301,12 @@ struct HostCtx {
             (void)hipFree(s.d_dig);
             (void)hipHostFree(s.h_ok);
             (void)hipFree(s.d_ok);
+            (void)hipHostFree(s.h_type);
+            (void)hipFree(s.d_type);
+            (void)hipHostFree(s.h_sum);
+            (void)hipFree(s.d_sum);
+            (void)hipHostFree(s.h_list);
+            (void)hipFree(s.d_list);
             if (s.stream) (void)hipStreamDestroy(s.stream);
         }
     }
@@ -538,6 +554,120 @@ int host_batch(int mode, const void* const* pages, uint64_t P, uint64_t n, int a
         if (!rc) rc = r2;
     }
     if (first_bad) *first_bad = bad;
+    return rc;
+}
+
+// Scrub's extra per-slot buffers: n type bytes, one summary, list_n indices.
+int ensure_scrub_slot(Slot& s, size_t n, size_t list_n) {
+    if (!s.h_sum) {
+        if (hipHostMalloc(reinterpret_cast<void**>(&s.h_sum), sizeof(pcs_scrub_summary), hipHostMallocDefault) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void**>(&s.d_sum), sizeof(pcs_scrub_summary)) != hipSuccess)
+            return fail(PCS_ERR_NOMEM, "scrub staging allocation failed");
+    }
+    if (n > s.cap_type) {
+        (void)hipHostFree(s.h_type);
+        (void)hipFree(s.d_type);
+        s.h_type = nullptr; s.d_type = nullptr;
+        s.cap_type = 0;
+        if (hipHostMalloc(reinterpret_cast<void**>(&s.h_type), n, hipHostMallocDefault) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void**>(&s.d_type), n) != hipSuccess)
+            return fail(PCS_ERR_NOMEM, "scrub staging allocation failed");
+        s.cap_type = n;
+    }
+    if (list_n > s.cap_list) {
+        (void)hipHostFree(s.h_list);
+        (void)hipFree(s.d_list);
+        s.h_list = nullptr; s.d_list = nullptr;
+        s.cap_list = 0;
+        if (hipHostMalloc(reinterpret_cast<void**>(&s.h_list), list_n * 8, hipHostMallocDefault) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void**>(&s.d_list), list_n * 8) != hipSuccess)
+            return fail(PCS_ERR_NOMEM, "scrub staging allocation failed");
+        s.cap_list = list_n;
+    }
+    return PCS_OK;
+}
+
+bool scrub_page_size_ok(uint64_t P) { return P >= 249 && P <= 0xFFFFFFFFull; }
+const char* const kScrubPageSize = "scrub needs 249 <= page_size < 2^32 (the XXH3 long path)";
+
+// pcs_pages_scrub_host: host_batch's staged pipeline (gather, or direct DMA of
+// a contiguous pinned run; never zero-copy, never the service) with the scrub
+// kernels per chunk.  Each chunk's classes, types, summary and list come back
+// with it and are merged, in page order, by ScrubMerge.
+int host_scrub(const void* const* pages, uint64_t P, uint64_t n, uint8_t* cls, uint8_t* type,
+               pcs_scrub_summary* summary, uint64_t* corrupt, uint64_t cap) {
+    if (int rc = require_device()) return rc;
+    if (!scrub_page_size_ok(P)) return fail(PCS_ERR_INVALID, kScrubPageSize);
+    if (int rc = check_host_batch_args(pages, P, n, PCS_XXH3_64)) return rc;
+    pcs::ScrubMerge merge(summary, corrupt, cap);
+    if (n == 0) return PCS_OK;
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return hip_fail(e, "hipGetDevice");
+    HostCtx& ctx = t_ctx[dev];
+    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(n, kStageBytes / P));
+    const uint64_t chunk_list = std::min(cap, chunk);
+    const uint8_t* base = static_cast<const uint8_t*>(pages[0]);
+    const bool direct = contiguous_pinned(pages, n, P);
+    for (auto& s : ctx.slot) {
+        if (int rc = ensure_slot(s, direct ? 0 : chunk * P, chunk)) return rc;
+        if (int rc = ensure_scrub_slot(s, chunk, chunk_list)) return rc;
+        if (direct && chunk * P > s.cap_dev_bytes) {  // device page buffers are still needed per slot
+            (void)hipFree(s.d_pages);
+            s.d_pages = nullptr;
+            s.cap_dev_bytes = 0;
+            if (hipMalloc(reinterpret_cast<void**>(&s.d_pages), chunk * P) != hipSuccess)
+                return fail(PCS_ERR_NOMEM, "staging allocation failed");
+            s.cap_dev_bytes = chunk * P;
+        }
+    }
+    auto drain = [&](Slot& s) -> int {
+        if (!s.busy) return PCS_OK;
+        const hipError_t err = hipStreamSynchronize(s.stream);
+        s.busy = false;
+        if (err != hipSuccess) return hip_fail(err, "hipStreamSynchronize");
+        std::memcpy(cls + s.first, s.h_ok, s.count);
+        if (type) std::memcpy(type + s.first, s.h_type, s.count);
+        merge.add(*s.h_sum, s.h_list, s.first);
+        return PCS_OK;
+    };
+    int rc = PCS_OK;
+    uint64_t k = 0;
+    for (uint64_t first = 0; first < n && rc == PCS_OK; first += chunk, ++k) {
+        Slot& s = ctx.slot[k % kSlots];
+        if ((rc = drain(s))) break;  // chunk k - kSlots: slots drain in page order
+        const uint64_t cnt = std::min(chunk, n - first);
+        if (!direct) gather(s.h_pages, pages, first, cnt, P);
+        count(direct ? PCS_COUNTER_DIRECT_DMA_CHUNKS : PCS_COUNTER_GATHER_CHUNKS);
+        s.first = first;
+        s.count = cnt;
+        s.listed = std::min(chunk_list, cnt);
+        e = hipMemcpyAsync(s.d_pages, direct ? base + first * P : s.h_pages, cnt * P, hipMemcpyHostToDevice, s.stream);
+        if (e == hipSuccess)
+            e = pcs::run_scrub(s.d_pages, P, cnt, s.d_ok, s.d_type, reinterpret_cast<uint64_t*>(s.d_sum), s.d_list,
+                               s.listed, s.stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(s.h_ok, s.d_ok, cnt, hipMemcpyDeviceToHost, s.stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(s.h_type, s.d_type, cnt, hipMemcpyDeviceToHost, s.stream);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(s.h_sum, s.d_sum, sizeof(pcs_scrub_summary), hipMemcpyDeviceToHost, s.stream);
+        if (e == hipSuccess && s.listed)
+            e = hipMemcpyAsync(s.h_list, s.d_list, s.listed * 8, hipMemcpyDeviceToHost, s.stream);
+        if (e != hipSuccess) {
+            rc = hip_fail(e, "host scrub enqueue");
+            break;
+        }
+        s.busy = true;
+    }
+    // oldest chunk first: slot k % kSlots holds chunk k - kSlots
+    for (int j = 0; j < kSlots; ++j) {
+        Slot& s = ctx.slot[(k + j) % kSlots];
+        if (rc == PCS_OK) {
+            rc = drain(s);
+        } else if (s.busy) {  // failed: let the slot's work finish, merge nothing more
+            (void)hipStreamSynchronize(s.stream);
+            s.busy = false;
+        }
+    }
     return rc;
 }
 
@@ -1401,6 +1531,32 @@ int pcs_pages_digest_dev(const void* d_pages, uint64_t page_size, uint64_t n_pag
 int pcs_pages_validate_dev(const void* d_pages, uint64_t page_size, uint64_t n_pages, int algo, uint8_t* d_ok,
                            uint64_t* d_first_bad, pcs_stream_t stream) {
     return pages_common(1, d_pages, page_size, n_pages, algo, nullptr, d_ok, d_first_bad, stream);
+}
+
+int pcs_pages_scrub_dev(const void* d_pages, uint64_t page_size, uint64_t n_pages, uint8_t* d_class, uint8_t* d_type,
+                        pcs_scrub_summary* d_summary, uint64_t* d_corrupt, uint64_t corrupt_cap,
+                        pcs_stream_t stream) {
+    static_assert(sizeof(pcs_scrub_summary) == 12 * sizeof(uint64_t), "pcs_scrub_summary is 12 x u64");
+    if (int rc = require_device()) return rc;
+    if (!scrub_page_size_ok(page_size)) return fail(PCS_ERR_INVALID, kScrubPageSize);
+    if (n_pages && !d_pages) return fail(PCS_ERR_INVALID, "d_pages is null");
+    if (n_pages && !d_class) return fail(PCS_ERR_INVALID, "d_class is null");
+    if (!d_summary) return fail(PCS_ERR_INVALID, "d_summary is null");
+    if (corrupt_cap && !d_corrupt) return fail(PCS_ERR_INVALID, "d_corrupt is null with corrupt_cap > 0");
+    if (n_pages > UINT64_MAX / page_size) return fail(PCS_ERR_INVALID, "n_pages * page_size overflows 64 bits");
+    return finish(pcs::run_scrub(static_cast<const uint8_t*>(d_pages), page_size, n_pages, d_class, d_type,
+                                 reinterpret_cast<uint64_t*>(d_summary), d_corrupt, corrupt_cap,
+                                 reinterpret_cast<hipStream_t>(stream)),
+                  "scrub kernel launch");
+}
+
+int pcs_pages_scrub_host(const void* const* pages, uint64_t page_size, uint64_t n_pages, uint8_t* cls, uint8_t* type,
+                         pcs_scrub_summary* summary, uint64_t* corrupt, uint64_t corrupt_cap) {
+    if (n_pages && !cls) return fail(PCS_ERR_INVALID, "cls is null");
+    if (!summary) return fail(PCS_ERR_INVALID, "summary is null");
+    if (corrupt_cap && !corrupt) return fail(PCS_ERR_INVALID, "corrupt is null with corrupt_cap > 0");
+    if (injected_failure()) return fail(PCS_ERR_HIP, "injected failure (PCS_TUNE_FAIL_INJECT)");
+    return host_scrub(pages, page_size, n_pages, cls, type, summary, corrupt, corrupt_cap);
 }
 
 int pcs_pages_stamp_dev(void* d_pages, uint64_t page_size, uint64_t n_pages, int algo, pcs_stream_t stream) {

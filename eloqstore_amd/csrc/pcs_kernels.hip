@@ -48,6 +48,13 @@ namespace pcs {
 // pass followed by k_scatter_stamp (pages_impl), because header writes
 // interleaved with the read stream cost 20 % at every rewrite width
 // (the in-place forms were retired in round 2).
+//
+// Scrub mode (kScrub, all three families): `ok` receives the page class and
+// the digest slot `out` carries the type-byte array instead (scrub_types);
+// no digest leaves the kernel.  A tile's class and type bytes are staged in
+// tile_h (class | type << 8) and leave as two coalesced 16-byte nt stores.
+__device__ __forceinline__ uint8_t* scrub_types(uint64_t* out) { return reinterpret_cast<uint8_t*>(out); }
+
 template <int P, int MODE, bool NT>
 __global__ __launch_bounds__(256) void k_xxh3_fixed(const uint8_t* __restrict__ pages, uint64_t n,
                                                    uint64_t* __restrict__ out, uint8_t* __restrict__ ok,
@@ -66,17 +73,30 @@ __global__ __launch_bounds__(256) void k_xxh3_fixed(const uint8_t* __restrict__ 
             const uint8_t* page = pages + pg * (uint64_t)P;
             uint64_t stored = 0;
             u32x4 first;
-            const uint64_t h = xxh3_page_fixed<P, NT>(page, L, stored, first);
-            if (L.g == 0) {
-                tile_h[grp] = h;
-                tile_ok[grp] = (h == stored) ? 1 : 0;
+            if constexpr (MODE == kScrub) {
+                ScrubProbe sp;
+                const uint64_t h = xxh3_page_fixed<P, NT, true>(page, L, stored, first, &sp);
+                const uint8_t cls = scrub_class(sp, h == stored);
+                if (L.g == 0) tile_h[grp] = (uint64_t)cls | ((uint64_t)sp.type << 8);
+            } else {
+                const uint64_t h = xxh3_page_fixed<P, NT>(page, L, stored, first);
+                if (L.g == 0) {
+                    tile_h[grp] = h;
+                    tile_ok[grp] = (h == stored) ? 1 : 0;
+                }
             }
         }
         __syncthreads();
         const uint64_t i = t * 16 + threadIdx.x;
         if (threadIdx.x < 16 && i < n) {
-            if (MODE == kDigest || out) st_nt(out + i, tile_h[threadIdx.x]);
-            if (MODE == kValidate) st_nt(ok + i, tile_ok[threadIdx.x]);
+            if constexpr (MODE == kScrub) {
+                const uint64_t ct = tile_h[threadIdx.x];
+                st_nt(ok + i, (uint8_t)ct);
+                st_nt(scrub_types(out) + i, (uint8_t)(ct >> 8));
+            } else {
+                if (MODE == kDigest || out) st_nt(out + i, tile_h[threadIdx.x]);
+                if (MODE == kValidate) st_nt(ok + i, tile_ok[threadIdx.x]);
+            }
         }
         if (MODE == kValidate && first_bad && threadIdx.x == 0) {
             // one note per tile: its smallest failing page
@@ -105,9 +125,13 @@ __global__ __launch_bounds__(256) void k_xxh3_fixed(const uint8_t* __restrict__ 
 // C the 16 slice carry words.  On return (after one block barrier) the page
 // digests and verdicts are in tile_h / tile_ok[ps]; the caller must barrier
 // before reading them.
-template <int P, bool NT, typename PageAt>
+// SCRUB: tile_h[ps] receives class | type << 8 instead of the digest.  A
+// slice whose first word is non-zero is not blank; the other slices OR their
+// words (the gate is uniform over the group), and every group publishes
+// "my slice is all zero" in Z[grp] for the chain group to combine.
+template <int P, bool NT, typename PageAt, bool SCRUB = false>
 __device__ __forceinline__ void xxh3_split_tile(const Xxh3Lane& L, PageAt page_at, uint64_t* S, uint64_t* C,
-                                                uint64_t* tile_h, uint8_t* tile_ok) {
+                                                uint64_t* tile_h, uint8_t* tile_ok, uint8_t* Z = nullptr) {
     static_assert(P % 4096 == 0 && P >= 8192 && P <= 65536, "split pages are 8..64 KiB");
     constexpr int G = P / 4096;       // groups per page
     constexpr int NB = P / 1024 - 1;  // full blocks (xxhash.h:5996); block NB is the final one, 4 chunks
@@ -115,6 +139,7 @@ __device__ __forceinline__ void xxh3_split_tile(const Xxh3Lane& L, PageAt page_a
     const int grp = threadIdx.x >> 4, ps = grp / G, j = grp % G, p = L.g & 3;
     const uint8_t* page = page_at(ps);
     uint64_t stored = 0;
+    [[maybe_unused]] uint32_t ptype = 0;  // SCRUB: page byte 8 (lane 0 of slice 0)
     if (page) {
         const u32x4* base = reinterpret_cast<const u32x4*>(page + 4096u * j) + L.g;
         u32x4 d[4][4];
@@ -124,6 +149,21 @@ __device__ __forceinline__ void xxh3_split_tile(const Xxh3Lane& L, PageAt page_a
             for (int c = 0; c < 4; ++c) d[i][c] = ld16<NT>(base + i * 64 + c * 16);
         stored = lo64(d[0][0]);
         if (L.g == 0) C[ps * G + j] = lo64(d[0][0]);
+        if constexpr (SCRUB) {
+            ScrubProbe sp;
+            scrub_probe_init(sp, L.g, d[0][0]);
+            ptype = sp.type;
+            if (sp.gate) {
+                uint32_t o = 0;
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) o |= or16(d[i][c]);
+                sp.orw = o;
+            }
+            const bool zero = sp.gate && row_or32(sp.gate ? sp.orw : 1u) == 0;
+            if (L.g == 0) Z[grp] = zero ? 1 : 0;
+        }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             uint64_t Te, To;
@@ -154,7 +194,15 @@ __device__ __forceinline__ void xxh3_split_tile(const Xxh3Lane& L, PageAt page_a
             Ao = xxh3_scramble(Ao + To, L.ks_o);
         }
         const uint64_t h = xxh3_merge(L, Ae + Sp[NB * 8], Ao + Sp[NB * 8 + 1], (uint64_t)(P - 8));
-        if (L.g == 0) {
+        if constexpr (SCRUB) {
+            if (L.g == 0) {
+                bool blank = true;
+#pragma unroll
+                for (int jj = 0; jj < G; ++jj) blank = blank && Z[ps * G + jj] != 0;
+                const uint8_t cls = (h == stored) ? kClassOk : blank ? kClassBlank : kClassCorrupt;
+                tile_h[ps] = (uint64_t)cls | ((uint64_t)ptype << 8);
+            }
+        } else if (L.g == 0) {
             tile_h[ps] = h;
             tile_ok[ps] = (h == stored) ? 1 : 0;
         }
@@ -170,23 +218,31 @@ __global__ __launch_bounds__(256) void k_xxh3_split(const uint8_t* __restrict__ 
     __shared__ uint64_t C[16];            // first input word of each slice (the previous block's carry)
     __shared__ uint64_t tile_h[16];
     __shared__ uint8_t tile_ok[16];
+    __shared__ uint8_t Z[MODE == kScrub ? 16 : 1];  // scrub: slice g is all zero
     const Xxh3Lane L = make_xxh3_lane(threadIdx.x & 15);
     const uint64_t ntiles = (n + PPB - 1) / PPB;
     const bool remap = gridDim.x == ntiles;
     for (uint64_t t0 = blockIdx.x; t0 < ntiles; t0 += gridDim.x) {
         const uint64_t t = remap ? xcd_tile(t0, ntiles) : t0;
-        xxh3_split_tile<P, NT>(
-            L,
-            [&](int ps) -> const uint8_t* {
-                const uint64_t pg = t * PPB + ps;
-                return pg < n ? pages + pg * (uint64_t)P : nullptr;
-            },
-            S, C, tile_h, tile_ok);
+        auto page_at = [&](int ps) -> const uint8_t* {
+            const uint64_t pg = t * PPB + ps;
+            return pg < n ? pages + pg * (uint64_t)P : nullptr;
+        };
+        if constexpr (MODE == kScrub)
+            xxh3_split_tile<P, NT, decltype(page_at), true>(L, page_at, S, C, tile_h, tile_ok, Z);
+        else
+            xxh3_split_tile<P, NT>(L, page_at, S, C, tile_h, tile_ok);
         __syncthreads();
         const uint64_t i0 = t * PPB;
         if (threadIdx.x < PPB && i0 + threadIdx.x < n) {
-            if (MODE == kDigest || out) st_nt(out + i0 + threadIdx.x, tile_h[threadIdx.x]);
-            if (MODE == kValidate) st_nt(ok + i0 + threadIdx.x, tile_ok[threadIdx.x]);
+            if constexpr (MODE == kScrub) {
+                const uint64_t ct = tile_h[threadIdx.x];
+                st_nt(ok + i0 + threadIdx.x, (uint8_t)ct);
+                st_nt(scrub_types(out) + i0 + threadIdx.x, (uint8_t)(ct >> 8));
+            } else {
+                if (MODE == kDigest || out) st_nt(out + i0 + threadIdx.x, tile_h[threadIdx.x]);
+                if (MODE == kValidate) st_nt(ok + i0 + threadIdx.x, tile_ok[threadIdx.x]);
+            }
         }
         if (MODE == kValidate && first_bad && threadIdx.x == 0) {
             for (int k = 0; k < PPB && i0 + k < n; ++k)
@@ -215,10 +271,22 @@ __global__ __launch_bounds__(256) void k_xxh3_stride(const uint8_t* __restrict__
         if (pg >= n) continue;
         const uint8_t* page = pages + pg * (uint64_t)P;
         uint64_t stored = 0;
-        const uint64_t h = BODY == 2   ? xxh3_page_any<NT>(page, P, L, stored)
-                           : BODY == 1 ? xxh3_page_rt4<NT>(page, P, L, stored)
-                                       : xxh3_page_rt<NT>(page, P, L, stored);
-        if (L.g == 0) emit(MODE, pg, h, stored, const_cast<uint8_t*>(page), out, ok, first_bad);
+        if constexpr (MODE == kScrub) {
+            ScrubProbe sp;
+            const uint64_t h = BODY == 2   ? xxh3_page_any<NT, true>(page, P, L, stored, &sp)
+                               : BODY == 1 ? xxh3_page_rt4<NT, true>(page, P, L, stored, &sp)
+                                           : xxh3_page_rt<NT, true>(page, P, L, stored, &sp);
+            const uint8_t cls = scrub_class(sp, h == stored);
+            if (L.g == 0) {
+                st_nt(ok + pg, cls);
+                st_nt(scrub_types(out) + pg, (uint8_t)sp.type);
+            }
+        } else {
+            const uint64_t h = BODY == 2   ? xxh3_page_any<NT>(page, P, L, stored)
+                               : BODY == 1 ? xxh3_page_rt4<NT>(page, P, L, stored)
+                                           : xxh3_page_rt<NT>(page, P, L, stored);
+            if (L.g == 0) emit(MODE, pg, h, stored, const_cast<uint8_t*>(page), out, ok, first_bad);
+        }
     }
 }
 
@@ -1207,6 +1275,178 @@ __global__ __launch_bounds__(256) void k_scatter_stamp_desc(uint8_t* __restrict_
     }
 }
 
+// ---------------------------------------------------------------------------
+// Scrub reduction (pcs_pages_scrub_dev): summary and the capped, ascending
+// list of corrupt pages from the class and type bytes the scrub pass wrote.
+// Pages are not read again.  Three launches, all ordered by construction (no
+// atomic append):
+//   k_scrub_count  one block per kScrubSpan pages: its counts and its first
+//                  corrupt page into a record;
+//   k_scrub_scan   one block: exclusive scan of the records' corrupt counts
+//                  (each block's rank in the list), the totals, the summary;
+//   k_scrub_list   one block per span again: the blocks whose rank is below
+//                  the cap scan their 16-page lane counts and write their
+//                  corrupt page indices at rank + position.
+// ---------------------------------------------------------------------------
+constexpr uint64_t kScrubSpan = 4096;  // pages per block: 256 lanes x 16 class bytes
+constexpr int kScrubRec = 10;          // u32 per record: corrupt, blank, ok_by_type[6], first corrupt, pad
+constexpr int kSummaryWords = 12;      // pcs_scrub_summary
+
+// 16 bytes at p, any alignment; bytes at cnt and beyond read as `fill`
+__device__ __forceinline__ void ld_bytes16(const uint8_t* p, uint64_t cnt, uint8_t fill, uint64_t& lo, uint64_t& hi) {
+    if (cnt >= 16) {
+        lo = ld64u(p);
+        hi = ld64u(p + 8);
+        return;
+    }
+    lo = hi = 0x0101010101010101ull * fill;
+    for (uint64_t k = 0; k < cnt; ++k) {
+        uint64_t& w = k < 8 ? lo : hi;
+        const int sh = 8 * (int)(k & 7);
+        w = (w & ~(0xFFull << sh)) | ((uint64_t)p[k] << sh);
+    }
+}
+__device__ __forceinline__ uint32_t byte_of(uint64_t lo, uint64_t hi, int k) {
+    return (uint32_t)((k < 8 ? lo >> (8 * k) : hi >> (8 * (k - 8))) & 0xFF);
+}
+
+// Exclusive scan of v over a 256-thread block (w4: four words of LDS, free
+// for reuse after the caller's next barrier); total receives the block sum.
+__device__ __forceinline__ uint64_t block_excl_scan(uint64_t v, uint64_t* w4, uint64_t& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint64_t incl = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t t = __shfl_up((unsigned long long)incl, d, 64);
+        if (lane >= d) incl += t;
+    }
+    if (lane == 63) w4[wave] = incl;
+    __syncthreads();
+    uint64_t before = 0;
+    total = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const uint64_t x = w4[w];
+        if (w < wave) before += x;
+        total += x;
+    }
+    return before + incl - v;
+}
+
+__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor((unsigned long long)v, d, 64);
+    return v;
+}
+
+__global__ __launch_bounds__(256) void k_scrub_count(const uint8_t* __restrict__ cls, const uint8_t* __restrict__ type,
+                                                    uint64_t n, uint32_t* __restrict__ rec) {
+    __shared__ uint32_t cnt[kScrubRec];
+    if (threadIdx.x < kScrubRec) cnt[threadIdx.x] = threadIdx.x == 8 ? 0xFFFFFFFFu : 0u;
+    __syncthreads();
+    const uint64_t p0 = (uint64_t)blockIdx.x * kScrubSpan + threadIdx.x * 16u;
+    // eight 8-bit counters (at most 16 each): corrupt, blank, ok by type bucket 0..5
+    uint64_t pack = 0;
+    uint32_t first = 0xFFFFFFFFu;
+    if (p0 < n) {
+        uint64_t cl, ch, tl, th;
+        ld_bytes16(cls + p0, n - p0, 0xFF, cl, ch);
+        ld_bytes16(type + p0, n - p0, 0, tl, th);
+#pragma unroll
+        for (int k = 15; k >= 0; --k) {
+            const uint32_t c = byte_of(cl, ch, k), t = byte_of(tl, th, k);
+            const int bucket = t < 4 ? (int)t : t == 255 ? 4 : 5;
+            const int field = c == kClassCorrupt ? 0 : c == kClassBlank ? 1 : 2 + bucket;
+            pack += (c <= kClassBlank) ? 1ull << (8 * field) : 0;
+            if (c == kClassCorrupt) first = threadIdx.x * 16u + k;
+        }
+    }
+    // widen to 16-bit counters (a span holds 4096 pages) and add up per wave
+    auto widen = [](uint32_t v) {
+        return (uint64_t)(v & 0xFF) | (uint64_t)((v >> 8) & 0xFF) << 16 | (uint64_t)((v >> 16) & 0xFF) << 32 |
+               (uint64_t)(v >> 24) << 48;
+    };
+    const uint64_t a = wave_sum(widen((uint32_t)pack)), b = wave_sum(widen((uint32_t)(pack >> 32)));
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int f = 0; f < 4; ++f) {
+            if (const uint32_t x = (uint32_t)(a >> (16 * f)) & 0xFFFF) atomicAdd(&cnt[f], x);
+            if (const uint32_t x = (uint32_t)(b >> (16 * f)) & 0xFFFF) atomicAdd(&cnt[4 + f], x);
+        }
+    }
+    if (first != 0xFFFFFFFFu) atomicMin(&cnt[8], first);
+    __syncthreads();
+    if (threadIdx.x < kScrubRec) rec[(uint64_t)blockIdx.x * kScrubRec + threadIdx.x] = cnt[threadIdx.x];
+}
+
+__global__ __launch_bounds__(256) void k_scrub_scan(const uint32_t* __restrict__ rec, uint64_t nblocks, uint64_t n,
+                                                   uint64_t cap, uint64_t* __restrict__ rank,
+                                                   uint64_t* __restrict__ summary) {
+    __shared__ uint64_t w4[4];
+    __shared__ unsigned long long tot[kSummaryWords];
+    if (threadIdx.x < kSummaryWords) tot[threadIdx.x] = threadIdx.x == 10 ? ~0ull : 0ull;
+    __syncthreads();
+    uint64_t corrupt = 0;   // corrupt pages in the spans before this round (uniform)
+    uint64_t acc[7] = {};   // blank, ok by type: this thread's spans
+    uint64_t first = ~0ull;
+    for (uint64_t base = 0; base < nblocks; base += 256) {
+        const uint64_t b = base + threadIdx.x;
+        uint64_t c = 0;
+        if (b < nblocks) {
+            const uint32_t* r = rec + b * kScrubRec;
+            c = r[0];
+#pragma unroll
+            for (int k = 0; k < 7; ++k) acc[k] += r[1 + k];
+            if (r[8] != 0xFFFFFFFFu && first == ~0ull) first = b * kScrubSpan + r[8];
+        }
+        uint64_t total;
+        const uint64_t before = block_excl_scan(c, w4, total);
+        if (b < nblocks) rank[b] = corrupt + before;
+        corrupt += total;
+        __syncthreads();
+    }
+#pragma unroll
+    for (int k = 0; k < 7; ++k) {
+        const uint64_t v = wave_sum(acc[k]);
+        if ((threadIdx.x & 63) == 0 && v) atomicAdd(&tot[3 + k], (unsigned long long)v);  // 3 blank, 4..9 ok by type
+    }
+    if (first != ~0ull) atomicMin(&tot[10], (unsigned long long)first);
+    __syncthreads();
+    if (threadIdx.x < kSummaryWords) {
+        const int i = threadIdx.x;
+        uint64_t v = tot[i];
+        if (i == 0) v = n;
+        if (i == 1) v = tot[4] + tot[5] + tot[6] + tot[7] + tot[8] + tot[9];
+        if (i == 2) v = corrupt;
+        if (i == 11) v = corrupt < cap ? corrupt : cap;
+        summary[i] = v;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_scrub_list(const uint8_t* __restrict__ cls, uint64_t n,
+                                                   const uint32_t* __restrict__ rec,
+                                                   const uint64_t* __restrict__ rank, uint64_t cap,
+                                                   uint64_t* __restrict__ list) {
+    __shared__ uint64_t w4[4];
+    const uint64_t r0 = rank[blockIdx.x];
+    if (rec[(uint64_t)blockIdx.x * kScrubRec] == 0 || r0 >= cap) return;  // uniform over the block
+    const uint64_t p0 = (uint64_t)blockIdx.x * kScrubSpan + threadIdx.x * 16u;
+    uint32_t mask = 0;
+    if (p0 < n) {
+        uint64_t cl, ch;
+        ld_bytes16(cls + p0, n - p0, 0xFF, cl, ch);
+#pragma unroll
+        for (int k = 0; k < 16; ++k) mask |= (byte_of(cl, ch, k) == kClassCorrupt ? 1u : 0u) << k;
+    }
+    uint64_t total;
+    uint64_t pos = r0 + block_excl_scan(__builtin_popcount(mask), w4, total);
+    while (mask && pos < cap) {
+        const int k = __builtin_ctz(mask);
+        mask &= mask - 1;
+        list[pos++] = p0 + k;
+    }
+}
+
 // Streaming-read ceiling, built on k_xxh3_fixed<4096>'s exact
 // structure (round 5's 64 KiB-window reader ran ~4 % below
 // the hash kernel it was meant to bound): 256-thread blocks of 16 four-KiB
@@ -1677,6 +1917,39 @@ hipError_t run_pages(int mode, int algo, const uint8_t* pages, uint64_t P, uint6
     hipLaunchKernelGGL(k_uniform_desc, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, P, n, off, len);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     return run_desc(mode, algo, pages, off, len, n, 8, 0, out, ok, fb, s);
+}
+
+// Scrub: the XXH3 page kernels in kScrub mode (one read of the pages; class
+// and type bytes out), then the ordered reduction over those bytes.  Nothing
+// here waits for the stream; n == 0 still writes the whole summary.
+hipError_t run_scrub(const uint8_t* pages, uint64_t P, uint64_t n, uint8_t* cls, uint8_t* type, uint64_t* summary,
+                     uint64_t* list, uint64_t cap, hipStream_t s) {
+    const uint64_t nblocks = (n + kScrubSpan - 1) / kScrubSpan;
+    if (nblocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    ScratchLease scratch(s);  // ranks, records and (when the caller wants no type bytes) the types
+    uint64_t* rank = nullptr;
+    uint32_t* rec = nullptr;
+    if (n) {
+        const size_t rec_bytes = (nblocks * kScrubRec * 4 + 7) & ~size_t(7);
+        hipError_t e = scratch.get(nblocks * 8 + rec_bytes + (type ? 0 : n));
+        if (e != hipSuccess) return e;
+        rank = static_cast<uint64_t*>(scratch.p);
+        rec = reinterpret_cast<uint32_t*>(rank + nblocks);
+        if (!type) type = reinterpret_cast<uint8_t*>(rec) + rec_bytes;
+        uint64_t* types_slot = reinterpret_cast<uint64_t*>(type);  // the digest slot carries the type array (scrub_types)
+        e = use_nt() ? launch_xxh3_pages<kScrub, true>(P, pages, n, types_slot, cls, nullptr, s)
+                     : launch_xxh3_pages<kScrub, false>(P, pages, n, types_slot, cls, nullptr, s);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_scrub_count, dim3((unsigned)nblocks), dim3(256), 0, s, cls, type, n, rec);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_scrub_scan, dim3(1), dim3(256), 0, s, rec, nblocks, n, cap, rank, summary);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && n && cap) {
+        hipLaunchKernelGGL(k_scrub_list, dim3((unsigned)nblocks), dim3(256), 0, s, cls, n, rec, rank, cap, list);
+        e = hipGetLastError();
+    }
+    return e;
 }
 
 hipError_t scratch_acquire(size_t bytes, void** out, int* id) { return g_scratch.acquire(bytes, out, id); }

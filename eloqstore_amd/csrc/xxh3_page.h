@@ -31,7 +31,12 @@ __constant__ KeyTables c_keys = make_tables();
 // XXH3_INIT_ACC (xxhash.h:6064-6065)
 __constant__ uint64_t c_init_acc[8] = {kP32_3, kP64_1, kP64_2, kP64_3, kP64_4, kP32_2, kP64_5, kP32_1};
 
-enum Mode : int { kDigest = 0, kValidate = 1, kStamp = 2 };
+enum Mode : int { kDigest = 0, kValidate = 1, kStamp = 2, kScrub = 3 };
+
+// Scrub classes (pcs_page_class, eloqstore_pcs.h): a page is OK when its
+// stored digest matches, BLANK when every one of its bytes (header included)
+// is zero, CORRUPT otherwise.
+constexpr uint8_t kClassCorrupt = 0, kClassOk = 1, kClassBlank = 2;
 
 // Native 16-byte vector (global_load_dwordx4).  NT selects the non-temporal
 // cache policy: every page byte is read exactly once, and the nt stream
@@ -44,6 +49,7 @@ __device__ __forceinline__ u32x4 ld16(const u32x4* p) {
     else return *p;
 }
 __device__ __forceinline__ uint64_t lo64(u32x4 v) { return ((uint64_t)v.y << 32) | v.x; }
+__device__ __forceinline__ uint32_t or16(u32x4 v) { return (v.x | v.y) | (v.z | v.w); }
 __device__ __forceinline__ uint64_t hi64(u32x4 v) { return ((uint64_t)v.w << 32) | v.z; }
 
 // Per-page output for every kernel: digest array, verdict array + first bad
@@ -76,6 +82,45 @@ __device__ __forceinline__ void emit(int mode, uint64_t idx, uint64_t h, uint64_
     } else {
         st_nt(out + idx, h);
     }
+}
+
+// Scrub mode's view of a page, filled by the page bodies below when their
+// SCRUB parameter is set (every other instantiation compiles it out).
+//   gate  the stored header [0, 8) is zero.  Uniform over the page's 16-lane
+//         group, and the only pages that can be blank: the OR below runs
+//         under it, so a page with a non-zero header pays for the gate alone.
+//   orw   OR of every 32-bit word this lane loaded (only maintained under
+//         gate).  The bodies load every page byte exactly once, overlapping
+//         last stripe and carry word included, so the page is blank iff the
+//         row-wide OR of orw is zero.
+//   type  page byte 8 (PageType), valid in lane 0 of the group.
+struct ScrubProbe {
+    bool gate;
+    uint32_t orw;
+    uint32_t type;
+};
+
+// OR over the 16 lanes of a DPP row, result in every lane
+__device__ __forceinline__ uint32_t row_or32(uint32_t v) {
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, kRowRor1, 0xF, 0xF, false);
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, kRowRor2, 0xF, 0xF, false);
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, kRowRor4, 0xF, 0xF, false);
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, kRowRor8, 0xF, 0xF, false);
+    return v;
+}
+
+// `head` is the lane's first 16 page bytes; lane 0's hold the header and the
+// type byte.
+__device__ __forceinline__ void scrub_probe_init(ScrubProbe& sp, int g, u32x4 head) {
+    sp.gate = row_or32(g == 0 ? (head.x | head.y) : 0u) == 0;
+    sp.orw = 0;
+    sp.type = head.z & 0xFFu;
+}
+
+// The page's class from its probe; call with the whole group active.
+__device__ __forceinline__ uint8_t scrub_class(const ScrubProbe& sp, bool digest_ok) {
+    const bool blank = sp.gate && row_or32(sp.gate ? sp.orw : 1u) == 0;
+    return digest_ok ? kClassOk : blank ? kClassBlank : kClassCorrupt;
 }
 
 // ---------------------------------------------------------------------------
@@ -186,9 +231,9 @@ __device__ __forceinline__ uint64_t xxh3_merge(const Xxh3Lane& L, uint64_t Ae, u
 // of block b (page word 128(b+1)) is lane 0's low half of chunk 0 of block
 // b+1, which lane 0 loads anyway: each batch also fetches chunk 0 of the
 // following block and hands it on, so no byte is loaded twice.
-template <int P, bool NT>
+template <int P, bool NT, bool SCRUB = false>
 __device__ __forceinline__ uint64_t xxh3_page_fixed(const uint8_t* __restrict__ page, const Xxh3Lane& L,
-                                                    uint64_t& stored, u32x4& first) {
+                                                    uint64_t& stored, u32x4& first, ScrubProbe* sp = nullptr) {
     constexpr int NB = (P - 9) / 1024;   // full blocks (xxhash.h:5996)
     constexpr int R = P / 256 - 4 * NB;  // chunks in the final block, 1..4
     constexpr int TB = NB + 1;
@@ -197,6 +242,7 @@ __device__ __forceinline__ uint64_t xxh3_page_fixed(const uint8_t* __restrict__ 
     u32x4 head = ld16<NT>(base);  // chunk 0 of the next block to fold
     stored = lo64(head);
     first = head;
+    if constexpr (SCRUB) scrub_probe_init(*sp, L.g, head);
 #pragma unroll
     for (int b0 = 0; b0 < TB; b0 += 4) {
         constexpr int kMaxBatch = 4;
@@ -226,6 +272,21 @@ __device__ __forceinline__ uint64_t xxh3_page_fixed(const uint8_t* __restrict__ 
                 Ao += To;
             }
         }
+        if constexpr (SCRUB) {
+            if (sp->gate) {  // every piece of this batch, d[0][0] (the head) included
+                uint32_t o = sp->orw;
+#pragma unroll
+                for (int i = 0; i < kMaxBatch; ++i) {
+                    const int b = b0 + i;
+                    if (b >= TB) break;
+                    const int nc = (b == NB) ? R : 4;
+#pragma unroll
+                    for (int c = 0; c < 4; ++c)
+                        if (c < nc) o |= or16(d[i][c]);
+                }
+                sp->orw = o;
+            }
+        }
         if (b0 + kMaxBatch < TB) head = d[kMaxBatch][0];
     }
     return xxh3_merge(L, Ae, Ao, (uint64_t)(P - 8));
@@ -233,9 +294,9 @@ __device__ __forceinline__ uint64_t xxh3_page_fixed(const uint8_t* __restrict__ 
 
 // Run-time page size (P % 256 == 0, P >= 256): one block per step, chunk 0 of
 // the next block prefetched with the current one (it supplies the carry).
-template <bool NT>
+template <bool NT, bool SCRUB = false>
 __device__ __forceinline__ uint64_t xxh3_page_rt(const uint8_t* __restrict__ page, uint32_t P, const Xxh3Lane& L,
-                                                 uint64_t& stored) {
+                                                 uint64_t& stored, ScrubProbe* sp = nullptr) {
     const int NB = (int)((P - 9) / 1024);
     const int R = (int)(P / 256) - 4 * NB;
     const u32x4* base = reinterpret_cast<const u32x4*>(page) + L.g;
@@ -243,6 +304,7 @@ __device__ __forceinline__ uint64_t xxh3_page_rt(const uint8_t* __restrict__ pag
     u32x4 d[4];
     d[0] = ld16<NT>(base);
     stored = lo64(d[0]);
+    if constexpr (SCRUB) scrub_probe_init(*sp, L.g, d[0]);
     for (int b = 0; b < NB; ++b) {
 #pragma unroll
         for (int c = 1; c < 4; ++c) d[c] = ld16<NT>(base + b * 64 + c * 16);
@@ -251,6 +313,9 @@ __device__ __forceinline__ uint64_t xxh3_page_rt(const uint8_t* __restrict__ pag
         xxh3_block_terms<false>(L, d, lo64(next0), 4, Te, To);
         Ae = xxh3_scramble(Ae + Te, L.ks_e);
         Ao = xxh3_scramble(Ao + To, L.ks_o);
+        if constexpr (SCRUB) {
+            if (sp->gate) sp->orw |= (or16(d[0]) | or16(d[1])) | (or16(d[2]) | or16(d[3]));
+        }
         d[0] = next0;
     }
 #pragma unroll
@@ -258,6 +323,13 @@ __device__ __forceinline__ uint64_t xxh3_page_rt(const uint8_t* __restrict__ pag
         if (c < R) d[c] = ld16<NT>(base + NB * 64 + c * 16);
     uint64_t Te, To;
     xxh3_block_terms<true>(L, d, 0, R, Te, To);
+    if constexpr (SCRUB) {
+        if (sp->gate) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if (c < R) sp->orw |= or16(d[c]);
+        }
+    }
     return xxh3_merge(L, Ae + Te, Ao + To, (uint64_t)(P - 8));
 }
 
@@ -266,9 +338,9 @@ __device__ __forceinline__ uint64_t xxh3_page_rt(const uint8_t* __restrict__ pag
 // batches keep as many bytes in flight as the fixed-size kernel.  Groups of a
 // wave may have different page sizes; the loop then runs to the largest with
 // the others masked.
-template <bool NT>
+template <bool NT, bool SCRUB = false>
 __device__ __forceinline__ uint64_t xxh3_page_rt4(const uint8_t* __restrict__ page, uint32_t P, const Xxh3Lane& L,
-                                                  uint64_t& stored) {
+                                                  uint64_t& stored, ScrubProbe* sp = nullptr) {
     const int NB = (int)((P - 9) / 1024);
     const int R = (int)(P / 256) - 4 * NB;
     const int TB = NB + 1;
@@ -276,6 +348,7 @@ __device__ __forceinline__ uint64_t xxh3_page_rt4(const uint8_t* __restrict__ pa
     uint64_t Ae = L.init_e, Ao = L.init_o;
     u32x4 head = ld16<NT>(base);
     stored = lo64(head);
+    if constexpr (SCRUB) scrub_probe_init(*sp, L.g, head);
     for (int b0 = 0; b0 < TB; b0 += 4) {
         u32x4 d[5][4];
         d[0][0] = head;
@@ -300,6 +373,20 @@ __device__ __forceinline__ uint64_t xxh3_page_rt4(const uint8_t* __restrict__ pa
                 xxh3_block_terms<true>(L, d[i], 0, R, Te, To);
                 Ae += Te;
                 Ao += To;
+            }
+        }
+        if constexpr (SCRUB) {
+            if (sp->gate) {  // the pieces this batch loaded, and its head
+                uint32_t o = sp->orw;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int b = b0 + i;
+                    const int nc = (b >= TB) ? 0 : (b == NB) ? R : 4;
+#pragma unroll
+                    for (int c = 0; c < 4; ++c)
+                        if (c < nc) o |= or16(d[i][c]);
+                }
+                sp->orw = o;
             }
         }
         head = d[4][0];
@@ -368,9 +455,9 @@ __device__ __forceinline__ void xxh3_final_terms(const Xxh3Lane& L, const u32x4 
 // xxh3_page_rt4's batches of four 1 KiB blocks, the final block's pieces
 // loaded in the same batch as the blocks before it (predicated per lane: only
 // pieces holding ordinary-stripe words), its terms by xxh3_final_terms.
-template <bool NT>
+template <bool NT, bool SCRUB = false>
 __device__ __forceinline__ uint64_t xxh3_page_any(const uint8_t* __restrict__ page, uint32_t P, const Xxh3Lane& L,
-                                                  uint64_t& stored) {
+                                                  uint64_t& stored, ScrubProbe* sp = nullptr) {
     const int NB = (int)((P - 9) / 1024);
     const int kmax = 4 * (int)((P - 9 - 1024u * (uint32_t)NB) / 64u);  // 0..60
     const int TB = NB + 1;
@@ -393,6 +480,13 @@ __device__ __forceinline__ uint64_t xxh3_page_any(const uint8_t* __restrict__ pa
         return v;
     };
     u32x4 head = NB > 0 ? ld16<NT>(base) : final_piece(0);
+    if constexpr (SCRUB) {
+        // every lane holds the header here; the pieces cover the page up to
+        // the end of the ordinary stripes, lastw (lanes 0-7) its last 64 bytes
+        sp->gate = stored == 0;
+        sp->orw = (uint32_t)lastw | (uint32_t)(lastw >> 32);
+        sp->type = head.z & 0xFFu;
+    }
     for (int b0 = 0; b0 < TB; b0 += 4) {
         u32x4 d[5][4];
         d[0][0] = head;
@@ -419,6 +513,16 @@ __device__ __forceinline__ uint64_t xxh3_page_any(const uint8_t* __restrict__ pa
                 xxh3_final_terms(L, d[i], kmax, lastw, Te, To);
                 Ae += Te;
                 Ao += To;
+            }
+        }
+        if constexpr (SCRUB) {
+            if (sp->gate) {  // pieces not loaded are zero-filled above
+                uint32_t o = sp->orw;
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) o |= or16(d[i][c]);
+                sp->orw = o;
             }
         }
         head = d[4][0];

@@ -105,6 +105,25 @@ void SetChecksums(std::span<char* const> pages, size_t page_size, PageHash hash 
 void PageDigests(std::span<const char* const> pages, size_t page_size, uint64_t* digests_out,
                  PageHash hash = PageHash::XXH3_64);
 
+// Scrub (pcs_pages_scrub_host): classifies every page as ok (stored digest
+// matches), blank (every byte zero: the never-written tail of a fallocated
+// data file) or corrupt, counts the ok pages by PageType (page byte 8) and
+// lists the corrupt ones.  XXH3 pages of at least 249 bytes only.
+struct ScrubReport {
+    uint64_t n_pages = 0, n_ok = 0, n_corrupt = 0, n_blank = 0;
+    // ok pages by type: NonLeafIndex, LeafIndex, Data, Overflow, Deleted (255), any other byte
+    uint64_t ok_by_type[6] = {};
+    uint64_t first_corrupt = UINT64_MAX;  // UINT64_MAX when none
+    std::vector<uint64_t> corrupt;        // the smallest corrupt page indices, ascending, at most max_listed
+    std::vector<uint8_t> page_class;      // pcs_page_class of every page
+    std::vector<uint8_t> page_type;       // byte 8 of every page
+};
+// PCS_OK or a negative pcs_status (message in LastChecksumError()); a failed
+// call leaves the report unspecified.
+int TryScrubPages(std::span<const char* const> pages, size_t page_size, ScrubReport& report,
+                  size_t max_listed = 1024);
+ScrubReport ScrubPages(std::span<const char* const> pages, size_t page_size, size_t max_listed = 1024);
+
 // Registers a page-pool chunk or io_uring buffer ring once (PagesPool::Extend,
 // src/storage/page.cpp:95-120): batches whose pages all lie in registered
 // memory are then hashed in place over PCIe in one launch, with no gather

@@ -95,8 +95,10 @@ enum pcs_flags {
  *      PCS_TUNE_SERVICE_SLOW_EXIT_TEST, PCS_TUNE_ZC_BATCH_EVENT, PCS_TUNE_SYNC_SPIN_US,
  *      PCS_TUNE_SERVICE_DEPARTURE, pcs_thread_prepare (additive);
  *      pcs_stream_read_dev writes
- *      one word per 4 KiB (was per 64 KiB: size d_out for the new count) */
-#define PCS_ABI_VERSION 6
+ *      one word per 4 KiB (was per 64 KiB: size d_out for the new count)
+ *   7  page scrub: pcs_pages_scrub_dev / pcs_pages_scrub_host, enum
+ *      pcs_page_class and struct pcs_scrub_summary; additive, no prototype changed */
+#define PCS_ABI_VERSION 7
 int pcs_abi_version(void);
 const char *pcs_version(void);
 const char *pcs_last_error(void);
@@ -122,6 +124,60 @@ int pcs_pages_validate_dev(const void *d_pages, uint64_t page_size, uint64_t n_p
 /* In place: page i bytes [0,8) = digest (LE); batched SetChecksum. */
 int pcs_pages_stamp_dev(void *d_pages, uint64_t page_size, uint64_t n_pages, int algo,
                         pcs_stream_t stream);
+
+/* ---- scrub: classify, census and list (XXH3 pages only) --------------------
+ * A whole-file check must tell pages that were never written from pages that
+ * are damaged: in append mode the store fallocates a data file to its full
+ * size, so a file that is not full ends in all-zero pages, and a zero page
+ * never validates (its stored digest is 0, XXH3 of a zero body is not).
+ *   PCS_PAGE_OK       the stored digest matches: exactly the pages for which
+ *                     pcs_pages_validate_dev writes 1
+ *   PCS_PAGE_BLANK    EVERY byte of the page, header included, is zero.  Exact:
+ *                     a zero body under its correct digest is OK, a zero header
+ *                     over any non-zero body byte is CORRUPT
+ *   PCS_PAGE_CORRUPT  neither
+ * d_class[i] receives the class and d_type[i] the raw page byte 8 (PageType,
+ * include/storage/page.h:14-21) of every page, whatever its class.  The
+ * summary counts the classes and, for OK pages only, the types: ok_by_type[0..3]
+ * = types 0..3 (NonLeafIndex, LeafIndex, Data, Overflow), [4] = type 255
+ * (Deleted), [5] = any other byte.  d_corrupt[0 .. n_listed) receives the
+ * n_listed = min(n_corrupt, corrupt_cap) SMALLEST corrupt page indices in
+ * ascending order (the same from call to call); entries at n_listed and beyond
+ * are not written; n_corrupt is always the full count.  Every call writes the
+ * whole summary, whatever it held before; n_pages == 0 gives zero counts and
+ * first_corrupt = UINT64_MAX.
+ *
+ * One pass reads every page byte once (the validate kernels with a second
+ * output byte and, only on pages whose stored header is zero, an OR over the
+ * loaded words); a second pass over the class and type bytes builds the
+ * summary and the list on the device.  page_size must be >= 249 (the XXH3 long
+ * path) and fit 32 bits, at any base alignment; anything else is
+ * PCS_ERR_INVALID.  Not scrubbed in this revision: mixed-size descriptors,
+ * XXH64 pages, the zero-copy page-list path, the validate service and
+ * pcs_batch objects.
+ *
+ * The _dev form enqueues on `stream` and never synchronises (its scratch is
+ * event-fenced per stream, so two streams may scrub concurrently); d_type may
+ * be NULL, d_corrupt may be NULL iff corrupt_cap == 0.  The _host form is
+ * synchronous and takes host pointers throughout: the pages go through the
+ * staged pipeline of the other host batches only (gathered, or one contiguous
+ * pinned run DMA'd directly, in 32 MiB chunks through the three slots; never
+ * zero-copy, never the service), classes and types come back per chunk, and
+ * the per-chunk summaries and lists are merged into global page indices,
+ * ascending and capped.  PCS_TUNE_FAIL_INJECT applies to it. */
+enum pcs_page_class { PCS_PAGE_CORRUPT = 0, PCS_PAGE_OK = 1, PCS_PAGE_BLANK = 2 };
+typedef struct pcs_scrub_summary { /* 12 x u64, the same layout on device and host */
+    uint64_t n_pages, n_ok, n_corrupt, n_blank;
+    uint64_t ok_by_type[6];
+    uint64_t first_corrupt; /* UINT64_MAX when none */
+    uint64_t n_listed;      /* min(n_corrupt, corrupt_cap) */
+} pcs_scrub_summary;
+int pcs_pages_scrub_dev(const void *d_pages, uint64_t page_size, uint64_t n_pages, uint8_t *d_class,
+                        uint8_t *d_type, pcs_scrub_summary *d_summary, uint64_t *d_corrupt,
+                        uint64_t corrupt_cap, pcs_stream_t stream);
+int pcs_pages_scrub_host(const void *const *pages, uint64_t page_size, uint64_t n_pages, uint8_t *cls,
+                         uint8_t *type, pcs_scrub_summary *summary, uint64_t *corrupt,
+                         uint64_t corrupt_cap);
 
 /* ---- device-resident descriptor batches (mixed page sizes) ----------------
  * Page i occupies [d_base + d_off[i], d_base + d_off[i] + d_len[i]).  Pages
@@ -354,7 +410,7 @@ int pcs_shard_range(uint64_t n, int world, int rank, uint64_t *begin, uint64_t *
  *                                     writing the request words (the kernel
  *                                     must ignore the torn line meanwhile)
  *   PCS_TUNE_FAIL_INJECT          [0] test only: the next k host-batch calls
- *                                     (pcs_pages_*_host, pcs_batch_submit*,
+ *                                     (pcs_pages_*_host scrub included, pcs_batch_submit*,
  *                                     pcs_batch_poll / wait,
  *                                     pcs_manifest_*_host) fail with
  *                                     PCS_ERR_HIP; decremented per failure

@@ -1,0 +1,108 @@
+"""Reference scrub classifier (numpy + the CPU oracle): what
+pcs_pages_scrub_dev / _host must return for a batch of fixed-size pages.
+
+Also the shared builders of the scrub tests' batches (hand-made pages of every
+class), so the CPU and GPU tests check the same cases.
+"""
+import numpy as np
+
+import oracle
+
+CORRUPT, OK, BLANK = 0, 1, 2
+NO_PAGE = (1 << 64) - 1
+TYPE_BYTES = (0, 1, 2, 3, 255, 9)  # one type byte per census bucket, in bucket order
+
+
+def bucket(t: int) -> int:
+    return t if t < 4 else 4 if t == 255 else 5
+
+
+def classify(pages: np.ndarray, page_size: int, corrupt_cap: int = 1024):
+    """pages: uint8 array of n * page_size bytes -> (cls, types, summary dict, corrupt list)."""
+    P = page_size
+    flat = np.ascontiguousarray(pages, dtype=np.uint8).reshape(-1)
+    n = flat.size // P
+    pg = flat[: n * P].reshape(n, P)
+    if n == 0:
+        empty = np.zeros(0, dtype=np.uint8)
+        return empty, empty, {"n_pages": 0, "n_ok": 0, "n_corrupt": 0, "n_blank": 0, "ok_by_type": [0] * 6,
+                              "first_corrupt": NO_PAGE, "n_listed": 0}, np.zeros(0, dtype=np.uint64)
+    digest = oracle.pages_digest(pg, P, 0)
+    stored = np.ascontiguousarray(pg[:, :8]).view("<u8").reshape(n)
+    ok = stored == digest
+    blank = ~pg.any(axis=1)
+    assert not (ok & blank).any()  # XXH3 of a zero body is never 0 (tests/golden/scrub_blank.json)
+    cls = np.where(ok, OK, np.where(blank, BLANK, CORRUPT)).astype(np.uint8)
+    types = pg[:, 8].copy()
+    by_type = [0] * 6
+    for t in types[ok]:
+        by_type[bucket(int(t))] += 1
+    bad = np.flatnonzero(cls == CORRUPT).astype(np.uint64)
+    summary = {"n_pages": n, "n_ok": int(ok.sum()), "n_corrupt": int(bad.size), "n_blank": int((cls == BLANK).sum()),
+               "ok_by_type": by_type, "first_corrupt": int(bad[0]) if bad.size else NO_PAGE,
+               "n_listed": int(min(bad.size, corrupt_cap))}
+    return cls, types, summary, bad[:corrupt_cap]
+
+
+def stamp(pg: np.ndarray, rows) -> None:
+    """Write the XXH3 digest of rows' bodies into their headers (SetChecksum)."""
+    rows = np.asarray(rows, dtype=np.int64)
+    if rows.size == 0:
+        return
+    P = pg.shape[1]
+    sub = np.ascontiguousarray(pg[rows])
+    pg[rows, :8] = oracle.pages_digest(sub, P, 0).astype("<u8").view(np.uint8).reshape(-1, 8)
+
+
+NEAR_BLANK_OFFSETS = (0, 7, 8, 9, 15, 16, 255, 256, 1023, 1024, 1032)
+
+
+def near_blank_offsets(P: int):
+    offs = list(NEAR_BLANK_OFFSETS) + [P // 2, P - 65, P - 64, P - 9, P - 8, P - 1]
+    return sorted({o for o in offs if 0 <= o < P})
+
+
+def build_batch(P: int, n: int, seed: int = 1, near=None, flips: int = 12, zero_header: bool = True):
+    """A mixed batch of n pages: OK pages of all six type buckets (type byte
+    set before stamping), `flips` pages corrupted by a flip at byte 10 (fewer
+    when n is small, at least one), blank pages (page 0, page n - 1 and one
+    whole 16-page tile: pages 32..47, or 0..15 when n < 64), a zero header
+    over a non-zero body, a zero body under its correct header, and one
+    near-blank page (zero but for one byte 0x01) per offset in `near`
+    (default: near_blank_offsets(P)).  Returns (pages (n, P) uint8, rows)."""
+    near = near_blank_offsets(P) if near is None else list(near)
+    rng = np.random.default_rng(seed * 1000003 + P * 31 + n)
+    pg = rng.integers(0, 256, size=(n, P), dtype=np.uint8)
+    pg[:, 8] = np.array(TYPE_BYTES, dtype=np.uint8)[np.arange(n) % 6]
+    stamp(pg, np.arange(n))
+    rows = {}
+    tile = list(range(32, 48)) if n >= 64 else list(range(0, 16))
+    rows["blank"] = sorted(set([0, n - 1] + tile))
+    free = [i for i in range(n) if i not in rows["blank"]]
+    rng.shuffle(free)
+    rows["ok_kept"] = [next(i for i in free if i % 6 == b) for b in range(6)]  # one untouched page per bucket
+    free = [i for i in free if i not in rows["ok_kept"]]
+    take = iter(free)
+    pg[rows["blank"]] = 0
+    rows["zero_body_ok"] = next(take)
+    pg[rows["zero_body_ok"]] = 0
+    stamp(pg, [rows["zero_body_ok"]])
+    rows["zero_header"] = None
+    if zero_header:
+        rows["zero_header"] = next(take)
+        pg[rows["zero_header"], :8] = 0
+    rows["near_blank"] = {}
+    for off in near:
+        r = next(take)
+        pg[r] = 0
+        pg[r, off] = 1
+        rows["near_blank"][off] = r
+    left = len(free) - 1 - (1 if zero_header else 0) - len(near)
+    assert left >= 1, "batch too small for its cases"
+    rows["flipped"] = sorted(next(take) for _ in range(min(flips, left)))
+    pg[rows["flipped"], 10] ^= 0xFF
+    if left - len(rows["flipped"]) >= 3:  # room left: a few more blank pages at random places
+        more = [next(take) for _ in range(3)]
+        pg[more] = 0
+        rows["blank"] = sorted(rows["blank"] + more)
+    return pg, rows

@@ -16,6 +16,11 @@
 //   page_checksum_tool --gen   <file_path> <n_pages> [page_size] [seed]
 //       write n synthetic pages (splitmix64 words, see include/eloqstore_pcs.h)
 //       and stamp them.
+//   page_checksum_tool --scrub <file_path> [page_size]   classify every page: ok,
+//       corrupted or blank (all zero: the never-written tail of a fallocated
+//       data file), count the ok pages by PageType and list up to 64
+//       corrupted offsets.  Exit 2 if any page is corrupted; blank pages do
+//       not fail a scrub (--scan counts them as corrupted).
 //   --scan/--stamp print a summary line with the GiB/s of the call; exit codes
 //   as above (--scan: 2 if any page is corrupted).
 #include <fcntl.h>
@@ -56,8 +61,9 @@ void usage(const char* prog) {
                  "Usage: %s <file_path> <offset_bytes> [page_size_bytes]\n"
                  "Offset and page size accept decimal or 0x-prefixed hex values.\n"
                  "       %s --scan|--stamp <file_path> [page_size_bytes]\n"
+                 "       %s --scrub <file_path> [page_size_bytes]\n"
                  "       %s --gen <file_path> <n_pages> [page_size_bytes] [seed]\n",
-                 prog, prog, prog);
+                 prog, prog, prog, prog);
 }
 
 constexpr uint64_t kDefaultPageSize = 4096;  // KvOptions{}.data_page_size
@@ -272,6 +278,107 @@ int bulk(bool stamp, const char* path, const char* size_s) {
     return bad ? 2 : 0;
 }
 
+// Blank-aware scrub: --scan's pinned double-buffered read loop with
+// pcs_pages_scrub_host per chunk.  The call is synchronous, so the overlap
+// comes from reading chunk k+1 on a helper thread while this thread scrubs
+// chunk k.  Never-written (all-zero) pages are counted, not failed; the first
+// kScrubLines corrupted pages are listed by offset.
+constexpr uint64_t kScrubLines = 64;
+
+int scrub(const char* path, const char* size_s) {
+    uint64_t P = kDefaultPageSize;
+    if (size_s && (!parse_u64(size_s, P) || P < 249 || P > 0xFFFFFFFFull)) {
+        std::fprintf(stderr, "Invalid page size: %s (scrub needs 249 <= page size < 2^32)\n", size_s);
+        return 1;
+    }
+    Fd f;
+    f.fd = open(path, O_RDONLY);
+    struct stat st;
+    if (f.fd < 0 || fstat(f.fd, &st) != 0) {
+        std::fprintf(stderr, "Failed to open %s: %s\n", path, std::strerror(errno));
+        return 1;
+    }
+    const uint64_t n = (uint64_t)st.st_size / P;  // a trailing partial page is ignored
+    if (n == 0) {
+        std::fprintf(stderr, "File %s holds no whole page of %llu bytes\n", path, (unsigned long long)P);
+        return 1;
+    }
+    const uint64_t chunk = std::max<uint64_t>(1, (env_u64("PCS_SCAN_CHUNK_MIB", 64) << 20) / P);
+    void* buf[2] = {nullptr, nullptr};
+    int rc = 0;
+    for (int k = 0; k < 2 && !rc; ++k) rc = pcs_host_alloc_pinned(chunk * P, &buf[k]);
+    if (rc) {
+        std::fprintf(stderr, "GPU setup failed (%d): %s\n", rc, pcs_last_error());
+        for (void* b : buf) pcs_host_free_pinned(b);
+        return 1;
+    }
+    std::vector<const void*> ptrs(std::min(chunk, n));
+    std::vector<uint8_t> cls(ptrs.size());
+    pcs_scrub_summary total{}, part{};
+    total.first_corrupt = UINT64_MAX;
+    uint64_t listed[kScrubLines];
+    {
+        // warm the GPU path before the clock starts, as --scan does
+        std::memset(buf[0], 0, (size_t)P);
+        const void* one = buf[0];
+        (void)pcs_pages_scrub_host(&one, P, 1, cls.data(), nullptr, &part, nullptr, 0);
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    auto read_chunk = [&](uint64_t p0, int s) {
+        return pread_parallel(f.fd, static_cast<char*>(buf[s]), std::min(chunk, n - p0) * P, p0 * P);
+    };
+    bool read_ok = read_chunk(0, 0);
+    uint64_t k = 0;
+    for (uint64_t p0 = 0; p0 < n && !rc; p0 += chunk, ++k) {
+        const int s = (int)(k & 1);
+        if (!read_ok) {
+            std::fprintf(stderr, "read failed at offset %llu: %s\n", (unsigned long long)(p0 * P), std::strerror(errno));
+            rc = 1;
+            break;
+        }
+        const uint64_t cnt = std::min(chunk, n - p0);
+        bool next_ok = true;
+        std::thread reader;
+        if (p0 + chunk < n) reader = std::thread([&, p0, s] { next_ok = read_chunk(p0 + chunk, s ^ 1); });
+        const char* b = static_cast<const char*>(buf[s]);
+        for (uint64_t i = 0; i < cnt; ++i) ptrs[i] = b + i * P;
+        const uint64_t room = kScrubLines - total.n_listed;
+        if (pcs_pages_scrub_host(ptrs.data(), P, cnt, cls.data(), nullptr, &part, room ? listed + total.n_listed : nullptr,
+                                 room)) {
+            rc = 1;
+        } else {
+            total.n_pages += part.n_pages;
+            total.n_ok += part.n_ok;
+            total.n_corrupt += part.n_corrupt;
+            total.n_blank += part.n_blank;
+            for (int t = 0; t < 6; ++t) total.ok_by_type[t] += part.ok_by_type[t];
+            for (uint64_t i = 0; i < part.n_listed; ++i) listed[total.n_listed + i] += p0;
+            total.n_listed += part.n_listed;
+        }
+        if (reader.joinable()) reader.join();
+        read_ok = next_ok;
+    }
+    const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    for (void* b : buf) pcs_host_free_pinned(b);
+    if (rc) {
+        std::fprintf(stderr, "scrub failed: %s\n", pcs_last_error());
+        return 1;
+    }
+    const double gib = (double)(n * P) / (1024.0 * 1024.0 * 1024.0);
+    std::printf("Scrubbed %llu pages of %llu bytes: %llu ok, %llu corrupted, %llu blank (%.3f s, %.2f GiB/s incl. file I/O)\n",
+                (unsigned long long)n, (unsigned long long)P, (unsigned long long)total.n_ok,
+                (unsigned long long)total.n_corrupt, (unsigned long long)total.n_blank, secs, gib / secs);
+    std::printf("ok by type: nonleaf_index=%llu leaf_index=%llu data=%llu overflow=%llu deleted=%llu other=%llu\n",
+                (unsigned long long)total.ok_by_type[0], (unsigned long long)total.ok_by_type[1],
+                (unsigned long long)total.ok_by_type[2], (unsigned long long)total.ok_by_type[3],
+                (unsigned long long)total.ok_by_type[4], (unsigned long long)total.ok_by_type[5]);
+    for (uint64_t i = 0; i < total.n_listed; ++i)
+        std::printf("corrupted page at offset %llu\n", (unsigned long long)(listed[i] * P));
+    if (total.n_corrupt > kScrubLines)
+        std::printf("... and %llu more corrupted pages\n", (unsigned long long)(total.n_corrupt - kScrubLines));
+    return total.n_corrupt ? 2 : 0;
+}
+
 int gen(const char* path, const char* n_s, const char* size_s, const char* seed_s) {
     uint64_t n = 0, P = kDefaultPageSize, seed = 0x5EED0001;
     if (!parse_u64(n_s, n) || n == 0 || (size_s && (!parse_u64(size_s, P) || P < 8 || P % 8)) ||
@@ -311,6 +418,13 @@ int main(int argc, char** argv) {
             return 1;
         }
         return bulk(argv[1][2] == 's' && argv[1][3] == 't', argv[2], argc == 4 ? argv[3] : nullptr);
+    }
+    if (argc >= 2 && !std::strcmp(argv[1], "--scrub")) {
+        if (argc < 3 || argc > 4) {
+            usage(argv[0]);
+            return 1;
+        }
+        return scrub(argv[2], argc == 4 ? argv[3] : nullptr);
     }
     if (argc >= 2 && !std::strcmp(argv[1], "--gen")) {
         if (argc < 4 || argc > 6) {
