@@ -50,6 +50,7 @@ def lib() -> ctypes.CDLL:
             "oracle_pages_digest": ([_vp, _sz, _sz, ctypes.c_int, _vp], None),
             "oracle_desc_digest": ([_vp, _vp, _vp, _sz, ctypes.c_int, _vp], None),
             "oracle_desc_raw_xxh3": ([_vp, _vp, _vp, _sz, _vp], None),
+            "oracle_desc_raw_xxh64": ([_vp, _vp, _vp, _sz, _u64, _vp], None),
             "oracle_fill_pages": ([_vp, _sz, _sz, _u64, _u64], None),
             "oracle_splitmix_word": ([_u64, _u64, _u64], _u64),
         }
@@ -122,6 +123,15 @@ def desc_raw_xxh3(base: np.ndarray, off: np.ndarray, length: np.ndarray) -> np.n
     length = np.ascontiguousarray(length, dtype=np.uint32)
     out = np.empty(len(off), dtype=np.uint64)
     lib().oracle_desc_raw_xxh3(base.ctypes.data, off.ctypes.data, length.ctypes.data, len(off), out.ctypes.data)
+    return out
+
+
+def desc_raw_xxh64(base: np.ndarray, off: np.ndarray, length: np.ndarray, seed: int = 0) -> np.ndarray:
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    length = np.ascontiguousarray(length, dtype=np.uint32)
+    out = np.empty(len(off), dtype=np.uint64)
+    lib().oracle_desc_raw_xxh64(base.ctypes.data, off.ctypes.data, length.ctypes.data, len(off), seed,
+                                out.ctypes.data)
     return out
 
 

@@ -308,6 +308,13 @@ void oracle_desc_raw_xxh3(const void *base, const uint64_t *off, const uint32_t 
     for (size_t i = 0; i < n; ++i) out[i] = oracle_xxh3_64(b + off[i], len[i]);
 }
 
+void oracle_desc_raw_xxh64(const void *base, const uint64_t *off, const uint32_t *len, size_t n,
+                           uint64_t seed, uint64_t *out)
+{
+    const uint8_t *b = (const uint8_t *)base;
+    for (size_t i = 0; i < n; ++i) out[i] = oracle_xxh64(b + off[i], len[i], seed);
+}
+
 /* ---- synthetic page generator ------------------------------------------ */
 
 uint64_t oracle_splitmix_word(uint64_t seed, uint64_t page_index, uint64_t word_index)

@@ -55,6 +55,8 @@ void oracle_desc_digest(const void *base, const uint64_t *off, const uint32_t *l
 /* Raw descriptor form: digest of the whole range (no 8-byte header skip). */
 void oracle_desc_raw_xxh3(const void *base, const uint64_t *off, const uint32_t *len,
                           size_t n, uint64_t *out);
+void oracle_desc_raw_xxh64(const void *base, const uint64_t *off, const uint32_t *len,
+                           size_t n, uint64_t seed, uint64_t *out);
 
 /* Synthetic page bytes shared with the device generator (pcs_fill_pages_dev):
  * word w of page p = splitmix64_mix((seed ^ p) + (w + 1) * 0x9E3779B97F4A7C15).

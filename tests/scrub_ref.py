@@ -17,6 +17,20 @@ def bucket(t: int) -> int:
     return t if t < 4 else 4 if t == 255 else 5
 
 
+BUCKET_OF = np.array([bucket(t) for t in range(256)], dtype=np.int64)  # type byte -> census bucket
+
+
+def summarize(cls: np.ndarray, types: np.ndarray, corrupt_cap: int = 1024):
+    """Summary dict and capped corrupt list of per-page classes and type bytes."""
+    ok = cls == OK
+    by_type = np.bincount(BUCKET_OF[types[ok]], minlength=6).tolist()
+    bad = np.flatnonzero(cls == CORRUPT).astype(np.uint64)
+    summary = {"n_pages": int(cls.size), "n_ok": int(ok.sum()), "n_corrupt": int(bad.size),
+               "n_blank": int((cls == BLANK).sum()), "ok_by_type": by_type,
+               "first_corrupt": int(bad[0]) if bad.size else NO_PAGE, "n_listed": int(min(bad.size, corrupt_cap))}
+    return summary, bad[:corrupt_cap]
+
+
 def classify(pages: np.ndarray, page_size: int, corrupt_cap: int = 1024):
     """pages: uint8 array of n * page_size bytes -> (cls, types, summary dict, corrupt list)."""
     P = page_size
@@ -34,14 +48,8 @@ def classify(pages: np.ndarray, page_size: int, corrupt_cap: int = 1024):
     assert not (ok & blank).any()  # XXH3 of a zero body is never 0 (tests/golden/scrub_blank.json)
     cls = np.where(ok, OK, np.where(blank, BLANK, CORRUPT)).astype(np.uint8)
     types = pg[:, 8].copy()
-    by_type = [0] * 6
-    for t in types[ok]:
-        by_type[bucket(int(t))] += 1
-    bad = np.flatnonzero(cls == CORRUPT).astype(np.uint64)
-    summary = {"n_pages": n, "n_ok": int(ok.sum()), "n_corrupt": int(bad.size), "n_blank": int((cls == BLANK).sum()),
-               "ok_by_type": by_type, "first_corrupt": int(bad[0]) if bad.size else NO_PAGE,
-               "n_listed": int(min(bad.size, corrupt_cap))}
-    return cls, types, summary, bad[:corrupt_cap]
+    summary, bad = summarize(cls, types, corrupt_cap)
+    return cls, types, summary, bad
 
 
 def stamp(pg: np.ndarray, rows) -> None:

@@ -15,6 +15,7 @@ import torch
 
 import eloqstore_amd as pcs
 import oracle
+from stream_ref import stream_fold
 from workload import mixed_layout, splitmix_words
 
 pytestmark = pytest.mark.gpu
@@ -503,23 +504,6 @@ def test_full_size_64k_chunks_sampled():
     torch.cuda.empty_cache()
 
 
-def _stream_fold(buf: np.ndarray) -> np.ndarray:
-    """What pcs_stream_read_dev computes per 4 KiB page: lane g of the page's
-    group folds its 16 pieces (bytes 256c + 16g) with xor/add, the 16 lanes
-    xor-reduced; a partial page reads only its whole 16 B pieces."""
-    nbytes = buf.nbytes - buf.nbytes % 16
-    npg = (nbytes + 4095) // 4096
-    pad = np.zeros(npg * 4096, dtype=np.uint8)
-    pad[:nbytes] = buf[:nbytes]
-    w = pad.view(np.uint32).reshape(npg, 16, 16, 4)  # page, chunk c, lane g, word
-    x = np.bitwise_xor.reduce(w[..., 0], axis=1).astype(np.uint64)
-    y = w[..., 1].astype(np.uint64).sum(axis=1) & 0xFFFFFFFF
-    z = np.bitwise_xor.reduce(w[..., 2], axis=1).astype(np.uint64)
-    ww = w[..., 3].astype(np.uint64).sum(axis=1) & 0xFFFFFFFF
-    r = ((x ^ z) << np.uint64(32)) | ((y + ww) & np.uint64(0xFFFFFFFF))
-    return np.bitwise_xor.reduce(r, axis=1)
-
-
 @pytest.mark.parametrize("nbytes", [16, 4096, 65536, 65536 * 7, 65536 * 300 + 4096 + 48, 65536 * 5 + 23,
                                     4096 * 17 + 4000])
 def test_stream_read_fold(nbytes):
@@ -531,7 +515,7 @@ def test_stream_read_fold(nbytes):
     out = torch.zeros(npg + 1, dtype=torch.int64, device=DEV)
     pcs.stream_read(buf, nbytes, out)
     got = u64(out)
-    assert np.array_equal(got[:npg], _stream_fold(host)) and got[npg] == 0
+    assert np.array_equal(got[:npg], stream_fold(host)) and got[npg] == 0
 
 
 @pytest.mark.parametrize("algo", [pcs.XXH3_64, pcs.XXH64])

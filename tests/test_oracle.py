@@ -98,6 +98,22 @@ def test_c_generator_matches_numpy():
         assert np.array_equal(a, b)
 
 
+def test_raw_range_batches_match_single_calls():
+    """desc_raw_xxh3 / desc_raw_xxh64 are loops over xxh3_64 / xxh64 (pinned
+    to the golden sweep above and, seeds included, to the compiled reference
+    below): overlapping ranges, any offset, lengths 0..100, seed 0 and a
+    non-zero seed."""
+    rng = np.random.default_rng(7)
+    buf = rng.integers(0, 256, size=4096, dtype=np.uint8)
+    offs = rng.integers(0, 4096 - 100, size=300).astype(np.uint64)
+    lens = rng.integers(0, 101, size=300).astype(np.uint32)
+    lens[:2] = [0, 100]
+    ranges = [buf[int(o):int(o) + int(L)] for o, L in zip(offs, lens)]
+    assert oracle.desc_raw_xxh3(buf, offs, lens).tolist() == [oracle.xxh3_64(r) for r in ranges]
+    for seed in (0, 0x9E3779B97F4A7C15):
+        assert oracle.desc_raw_xxh64(buf, offs, lens, seed).tolist() == [oracle.xxh64(r, seed) for r in ranges]
+
+
 @pytest.mark.skipif(oracle.ref_lib() is None, reason="oracle/_ref not built (reference tree absent)")
 def test_oracle_vs_compiled_reference_random():
     ref = oracle.ref_lib()
