@@ -49,6 +49,8 @@ _SIGS = {
     "pcs_pages_stamp_dev": [_vp, _u64, _u64, _i32, _vp],
     "pcs_pages_scrub_dev": [_vp, _u64, _u64, _vp, _vp, _vp, _vp, _u64, _vp],
     "pcs_pages_scrub_host": [_vp, _u64, _u64, _vp, _vp, _vp, _vp, _u64],
+    "pcs_scrub_extents_dev": [_vp, _u64, _vp, _vp, _u64, _vp],
+    "pcs_pages_scrub_extents_host": [_vp, _u64, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64],
     "pcs_desc_digest_dev": [_vp, _vp, _vp, _u64, _i32, _vp, _vp],
     "pcs_desc_validate_dev": [_vp, _vp, _vp, _u64, _i32, _vp, _vp, _vp],
     "pcs_desc_stamp_dev": [_vp, _vp, _vp, _u64, _i32, _vp],
@@ -293,6 +295,48 @@ def pages_scrub(pages, page_size: int, n: int, cls=None, types=None, corrupt_cap
     return cls, types, d, listed
 
 
+_EXTENT_WORDS = 12  # pcs_extent_summary
+_EXTENT_FIELDS = ("n_pages", "n_runs", "n_listed", "written_pages", "n_blank", "n_blank_runs", "first_blank",
+                  "n_holes", "n_hole_pages", "first_hole", "first_class", "last_class")
+# pcs_extent: 24 bytes, 3 u64 words on the device
+EXTENT_DTYPE = np.dtype([("first_page", "<u8"), ("n_pages", "<u8"), ("cls", "<u4"), ("reserved", "<u4")])
+
+
+def extent_dict(words) -> dict:
+    """pcs_extent_summary (12 u64 words) as a dict."""
+    return {k: int(x) & NO_PAGE for k, x in zip(_EXTENT_FIELDS, words)}
+
+
+def scrub_extents_async(cls, n: int | None = None, summary=None, runs=None, run_cap: int = 1024, stream=None):
+    """pcs_scrub_extents_dev, enqueue only: cls is a device uint8 tensor of
+    class bytes (or any slice of one); returns the device tensors (summary
+    words, runs as run_cap x 3 int64 words), valid once the stream is
+    synchronised.  run_cap 0 passes a NULL run list."""
+    if n is None:
+        n = cls.numel()
+    if summary is None:
+        summary = torch.empty(_EXTENT_WORDS, dtype=torch.int64, device=cls.device)
+    if runs is None and run_cap:
+        runs = torch.empty((run_cap, 3), dtype=torch.int64, device=cls.device)
+    _call("pcs_scrub_extents_dev", _ptr(cls), n, _ptr(summary), _ptr(runs) if run_cap else 0, run_cap,
+          _stream(stream))
+    return summary, runs
+
+
+def scrub_extents(cls, n: int | None = None, run_cap: int = 1024, stream=None):
+    """The maximal runs of equal class in a scrub's class bytes and the
+    written extent / blank tail / holes summary: -> (summary dict, structured
+    array (EXTENT_DTYPE) of the n_listed first runs).  Waits for the stream."""
+    summary, runs = scrub_extents_async(cls, n, None, None, run_cap, stream)
+    if stream is not None:  # the copies below are ordered on torch's current stream only
+        _call("pcs_synchronize", _stream(stream))
+    d = extent_dict(summary.cpu().tolist())
+    if runs is None or d["n_listed"] == 0:
+        return d, np.zeros(0, dtype=EXTENT_DTYPE)
+    words = np.ascontiguousarray(runs[: d["n_listed"]].cpu().numpy())
+    return d, words.view(EXTENT_DTYPE).reshape(-1)
+
+
 def desc_digest(base, off, length, n: int, algo: int = XXH3_64, out=None, stream=None):
     if out is None:
         out = torch.empty(n, dtype=torch.int64, device=base.device)
@@ -529,6 +573,34 @@ def scrub_pages_host(pages: list, page_size: int, corrupt_cap: int = 1024):
     arr, _keep = _page_ptrs(pages)
     ptrs = np.array([arr[i] or 0 for i in range(len(pages))], dtype=np.uint64)
     return scrub_ptrs(ptrs, page_size, corrupt_cap)
+
+
+def scrub_extents_ptrs(ptrs, page_size: int, run_cap: int = 1024, corrupt_cap: int = 1024, per_page: bool = False):
+    """pcs_pages_scrub_extents_host over raw host page addresses ->
+    (summary dict, corrupt index array, extent summary dict, runs array) and,
+    with per_page, the cls and types arrays behind them (NULL otherwise)."""
+    ptrs = np.ascontiguousarray(ptrs, dtype=np.uint64)
+    n = len(ptrs)
+    cls = np.zeros(max(1, n), dtype=np.uint8) if per_page else None
+    types = np.zeros(max(1, n), dtype=np.uint8) if per_page else None
+    summary = np.zeros(_SUMMARY_WORDS, dtype=np.uint64)
+    corrupt = np.zeros(max(1, corrupt_cap), dtype=np.uint64)
+    ext = np.zeros(_EXTENT_WORDS, dtype=np.uint64)
+    runs = np.zeros(max(1, run_cap), dtype=EXTENT_DTYPE)
+    _call("pcs_pages_scrub_extents_host", ptrs.ctypes.data, page_size, n, cls.ctypes.data if per_page else 0,
+          types.ctypes.data if per_page else 0, summary.ctypes.data, corrupt.ctypes.data if corrupt_cap else 0,
+          corrupt_cap, ext.ctypes.data, runs.ctypes.data if run_cap else 0, run_cap)
+    d, e = summary_dict(summary), extent_dict(ext)
+    out = (d, corrupt[: d["n_listed"]], e, runs[: e["n_listed"]])
+    return out + (cls[:n], types[:n]) if per_page else out
+
+
+def scrub_extents_host(pages: list, page_size: int, run_cap: int = 1024, corrupt_cap: int = 1024,
+                       per_page: bool = False):
+    """Scrub scattered host buffers (bytearrays) with extents: see scrub_extents_ptrs."""
+    arr, _keep = _page_ptrs(pages)
+    ptrs = np.array([arr[i] or 0 for i in range(len(pages))], dtype=np.uint64)
+    return scrub_extents_ptrs(ptrs, page_size, run_cap, corrupt_cap, per_page)
 
 
 class ValidateService:

@@ -22,7 +22,15 @@ hipError_t run_pages(int mode, int algo, const uint8_t* pages, uint64_t page_siz
 hipError_t run_scrub(const uint8_t* pages, uint64_t page_size, uint64_t n, uint8_t* cls, uint8_t* type,
                      uint64_t* summary, uint64_t* list, uint64_t cap, hipStream_t s);
 
-// Descriptor batch: range i = [base + off[i], +len[i]).  skip = 8 applies the
+// Extents of the class bytes cls[0 .. n) (a scrub's, or any sub-range of them
+// at any byte alignment): summary = the 12 words of pcs_extent_summary,
+// runs[0 .. min(n_runs, cap)) = the first maximal runs of equal byte as
+// pcs_extent, each with its full length.  All device memory; enqueues on s
+// and never waits.
+hipError_t run_extents(const uint8_t* cls, uint64_t n, uint64_t* summary, uint64_t* runs, uint64_t cap,
+                       hipStream_t s);
+
+// Descriptor batch: range i =[base + off[i], +len[i]).  skip = 8 applies the
 // page convention (digest over [8, len), stored digest at [0, 8)); skip = 0
 // hashes the raw range.  seed is used by XXH64 only (XXH3 path is seed 0).
 hipError_t run_desc(int mode, int algo, const uint8_t* base, const uint64_t* off, const uint32_t* len, uint64_t n,

@@ -83,6 +83,43 @@ ScrubReport ScrubPages(std::span<const char* const> pages, size_t page_size, siz
     return report;
 }
 
+int TryScrubExtents(std::span<const char* const> pages, size_t page_size, ExtentReport& report, size_t max_runs,
+                    size_t max_listed) {
+    const size_t n = pages.size();
+    report.corrupt.assign(std::min(max_listed, n), 0);
+    std::vector<pcs_extent> runs(std::min(max_runs, n));
+    pcs_scrub_summary sum{};
+    pcs_extent_summary ext{};
+    const int rc = pcs_pages_scrub_extents_host(reinterpret_cast<const void* const*>(pages.data()), page_size, n,
+                                                nullptr, nullptr, &sum, report.corrupt.data(), report.corrupt.size(),
+                                                &ext, runs.data(), runs.size());
+    if (rc != PCS_OK) return rc;
+    report.n_pages = sum.n_pages;
+    report.n_ok = sum.n_ok;
+    report.n_corrupt = sum.n_corrupt;
+    report.n_blank = sum.n_blank;
+    for (int k = 0; k < 6; ++k) report.ok_by_type[k] = sum.ok_by_type[k];
+    report.first_corrupt = sum.first_corrupt;
+    report.corrupt.resize(sum.n_listed);
+    report.n_runs = ext.n_runs;
+    report.written_pages = ext.written_pages;
+    report.n_blank_runs = ext.n_blank_runs;
+    report.first_blank = ext.first_blank;
+    report.n_holes = ext.n_holes;
+    report.n_hole_pages = ext.n_hole_pages;
+    report.first_hole = ext.first_hole;
+    report.runs.resize(ext.n_listed);
+    for (size_t i = 0; i < report.runs.size(); ++i)
+        report.runs[i] = PageExtent{runs[i].first_page, runs[i].n_pages, static_cast<uint8_t>(runs[i].cls)};
+    return PCS_OK;
+}
+
+ExtentReport ScrubExtents(std::span<const char* const> pages, size_t page_size, size_t max_runs, size_t max_listed) {
+    ExtentReport report;
+    if (int rc = TryScrubExtents(pages, page_size, report, max_runs, max_listed)) die("ScrubExtents", rc);
+    return report;
+}
+
 void RegisterPagePool(void* base, size_t bytes) {
     if (int rc = pcs_host_register(base, bytes)) die("RegisterPagePool", rc);
 }

@@ -7,6 +7,7 @@
 #include "eloqstore_pcs.h"
 #include "eloqstore_pcs_internal.h"
 #include "region_registry.h"
+#include "extent_merge.h"
 #include "scrub_merge.h"
 
 #include <hip/hip_runtime.h>
@@ -283,6 +284,13 @@ struct Slot {
     uint64_t* d_list = nullptr;
     size_t cap_type = 0, cap_list = 0;
     uint64_t listed = 0;  // list entries asked of the chunk in flight
+    // scrub extents only (ensure_extent_slot): the chunk's extent summary and its run list
+    pcs_extent_summary* h_ext = nullptr;  // pinned
+    pcs_extent_summary* d_ext = nullptr;
+    pcs_extent* h_runs = nullptr;  // pinned
+    pcs_extent* d_runs = nullptr;
+    size_t cap_runs = 0;
+    uint64_t runs_listed = 0;  // runs asked of the chunk in flight
 };
 
 constexpr int kSlots = 3;  // H2D of chunk k+1 || kernel k || D2H k-1
@@ -307,6 +315,10 @@ struct HostCtx {
             (void)hipFree(s.d_sum);
             (void)hipHostFree(s.h_list);
             (void)hipFree(s.d_list);
+            (void)hipHostFree(s.h_ext);
+            (void)hipFree(s.d_ext);
+            (void)hipHostFree(s.h_runs);
+            (void)hipFree(s.d_runs);
             if (s.stream) (void)hipStreamDestroy(s.stream);
         }
     }
@@ -587,6 +599,26 @@ int ensure_scrub_slot(Slot& s, size_t n, size_t list_n) {
     return PCS_OK;
 }
 
+// The extents' extra per-slot buffers: one extent summary, runs_n runs.
+int ensure_extent_slot(Slot& s, size_t runs_n) {
+    if (!s.h_ext) {
+        if (hipHostMalloc(reinterpret_cast<void**>(&s.h_ext), sizeof(pcs_extent_summary), hipHostMallocDefault) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void**>(&s.d_ext), sizeof(pcs_extent_summary)) != hipSuccess)
+            return fail(PCS_ERR_NOMEM, "scrub staging allocation failed");
+    }
+    if (runs_n > s.cap_runs) {
+        (void)hipHostFree(s.h_runs);
+        (void)hipFree(s.d_runs);
+        s.h_runs = nullptr; s.d_runs = nullptr;
+        s.cap_runs = 0;
+        if (hipHostMalloc(reinterpret_cast<void**>(&s.h_runs), runs_n * sizeof(pcs_extent), hipHostMallocDefault) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void**>(&s.d_runs), runs_n * sizeof(pcs_extent)) != hipSuccess)
+            return fail(PCS_ERR_NOMEM, "scrub staging allocation failed");
+        s.cap_runs = runs_n;
+    }
+    return PCS_OK;
+}
+
 bool scrub_page_size_ok(uint64_t P) { return P >= 249 && P <= 0xFFFFFFFFull; }
 const char* const kScrubPageSize = "scrub needs 249 <= page_size < 2^32 (the XXH3 long path)";
 
@@ -594,12 +626,20 @@ const char* const kScrubPageSize = "scrub needs 249 <= page_size < 2^32 (the XXH
 // a contiguous pinned run; never zero-copy, never the service) with the scrub
 // kernels per chunk.  Each chunk's classes, types, summary and list come back
 // with it and are merged, in page order, by ScrubMerge.
+// pcs_pages_scrub_extents_host (ext non-null) shares the loop: behind each
+// chunk's scrub the extent kernels run on the chunk's class bytes while they
+// are on the device, the chunk's extent summary and run list come back too and
+// ExtentMerge folds them; cls may then be null (classes and types stay on the
+// device).
 int host_scrub(const void* const* pages, uint64_t P, uint64_t n, uint8_t* cls, uint8_t* type,
-               pcs_scrub_summary* summary, uint64_t* corrupt, uint64_t cap) {
+               pcs_scrub_summary* summary, uint64_t* corrupt, uint64_t cap, pcs_extent_summary* ext = nullptr,
+               pcs_extent* runs = nullptr, uint64_t run_cap = 0) {
     if (int rc = require_device()) return rc;
     if (!scrub_page_size_ok(P)) return fail(PCS_ERR_INVALID, kScrubPageSize);
     if (int rc = check_host_batch_args(pages, P, n, PCS_XXH3_64)) return rc;
     pcs::ScrubMerge merge(summary, corrupt, cap);
+    pcs_extent_summary no_ext;
+    pcs::ExtentMerge ext_merge(ext ? ext : &no_ext, runs, run_cap);
     if (n == 0) return PCS_OK;
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
@@ -607,11 +647,15 @@ int host_scrub(const void* const* pages, uint64_t P, uint64_t n, uint8_t* cls, u
     HostCtx& ctx = t_ctx[dev];
     const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(n, kStageBytes / P));
     const uint64_t chunk_list = std::min(cap, chunk);
+    const uint64_t chunk_runs = pcs::ExtentMerge::chunk_cap(run_cap, chunk);
     const uint8_t* base = static_cast<const uint8_t*>(pages[0]);
     const bool direct = contiguous_pinned(pages, n, P);
     for (auto& s : ctx.slot) {
         if (int rc = ensure_slot(s, direct ? 0 : chunk * P, chunk)) return rc;
         if (int rc = ensure_scrub_slot(s, chunk, chunk_list)) return rc;
+        if (ext) {
+            if (int rc = ensure_extent_slot(s, chunk_runs)) return rc;
+        }
         if (direct && chunk * P > s.cap_dev_bytes) {  // device page buffers are still needed per slot
             (void)hipFree(s.d_pages);
             s.d_pages = nullptr;
@@ -626,9 +670,10 @@ int host_scrub(const void* const* pages, uint64_t P, uint64_t n, uint8_t* cls, u
         const hipError_t err = hipStreamSynchronize(s.stream);
         s.busy = false;
         if (err != hipSuccess) return hip_fail(err, "hipStreamSynchronize");
-        std::memcpy(cls + s.first, s.h_ok, s.count);
+        if (cls) std::memcpy(cls + s.first, s.h_ok, s.count);
         if (type) std::memcpy(type + s.first, s.h_type, s.count);
         merge.add(*s.h_sum, s.h_list, s.first);
+        if (ext) ext_merge.add(*s.h_ext, s.h_runs, s.first);
         return PCS_OK;
     };
     int rc = PCS_OK;
@@ -646,12 +691,22 @@ int host_scrub(const void* const* pages, uint64_t P, uint64_t n, uint8_t* cls, u
         if (e == hipSuccess)
             e = pcs::run_scrub(s.d_pages, P, cnt, s.d_ok, s.d_type, reinterpret_cast<uint64_t*>(s.d_sum), s.d_list,
                                s.listed, s.stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(s.h_ok, s.d_ok, cnt, hipMemcpyDeviceToHost, s.stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(s.h_type, s.d_type, cnt, hipMemcpyDeviceToHost, s.stream);
+        if (ext && e == hipSuccess) {
+            s.runs_listed = pcs::ExtentMerge::chunk_cap(run_cap, cnt);
+            e = pcs::run_extents(s.d_ok, cnt, reinterpret_cast<uint64_t*>(s.d_ext),
+                                 reinterpret_cast<uint64_t*>(s.d_runs), s.runs_listed, s.stream);
+        }
+        if (e == hipSuccess && (cls || !ext)) e = hipMemcpyAsync(s.h_ok, s.d_ok, cnt, hipMemcpyDeviceToHost, s.stream);
+        if (e == hipSuccess && (type || !ext))
+            e = hipMemcpyAsync(s.h_type, s.d_type, cnt, hipMemcpyDeviceToHost, s.stream);
         if (e == hipSuccess)
             e = hipMemcpyAsync(s.h_sum, s.d_sum, sizeof(pcs_scrub_summary), hipMemcpyDeviceToHost, s.stream);
         if (e == hipSuccess && s.listed)
             e = hipMemcpyAsync(s.h_list, s.d_list, s.listed * 8, hipMemcpyDeviceToHost, s.stream);
+        if (ext && e == hipSuccess)
+            e = hipMemcpyAsync(s.h_ext, s.d_ext, sizeof(pcs_extent_summary), hipMemcpyDeviceToHost, s.stream);
+        if (ext && e == hipSuccess && s.runs_listed)
+            e = hipMemcpyAsync(s.h_runs, s.d_runs, s.runs_listed * sizeof(pcs_extent), hipMemcpyDeviceToHost, s.stream);
         if (e != hipSuccess) {
             rc = hip_fail(e, "host scrub enqueue");
             break;
@@ -1557,6 +1612,31 @@ int pcs_pages_scrub_host(const void* const* pages, uint64_t page_size, uint64_t 
     if (corrupt_cap && !corrupt) return fail(PCS_ERR_INVALID, "corrupt is null with corrupt_cap > 0");
     if (injected_failure()) return fail(PCS_ERR_HIP, "injected failure (PCS_TUNE_FAIL_INJECT)");
     return host_scrub(pages, page_size, n_pages, cls, type, summary, corrupt, corrupt_cap);
+}
+
+int pcs_scrub_extents_dev(const uint8_t* d_class, uint64_t n_pages, pcs_extent_summary* d_summary, pcs_extent* d_runs,
+                          uint64_t run_cap, pcs_stream_t stream) {
+    static_assert(sizeof(pcs_extent_summary) == 12 * sizeof(uint64_t), "pcs_extent_summary is 12 x u64");
+    static_assert(sizeof(pcs_extent) == 3 * sizeof(uint64_t), "pcs_extent is first_page, n_pages, cls | reserved");
+    if (int rc = require_device()) return rc;
+    if (n_pages && !d_class) return fail(PCS_ERR_INVALID, "d_class is null");
+    if (!d_summary) return fail(PCS_ERR_INVALID, "d_summary is null");
+    if (run_cap && !d_runs) return fail(PCS_ERR_INVALID, "d_runs is null with run_cap > 0");
+    return finish(pcs::run_extents(d_class, n_pages, reinterpret_cast<uint64_t*>(d_summary),
+                                   reinterpret_cast<uint64_t*>(d_runs), run_cap,
+                                   reinterpret_cast<hipStream_t>(stream)),
+                  "scrub extents kernel launch");
+}
+
+int pcs_pages_scrub_extents_host(const void* const* pages, uint64_t page_size, uint64_t n_pages, uint8_t* cls,
+                                 uint8_t* type, pcs_scrub_summary* summary, uint64_t* corrupt, uint64_t corrupt_cap,
+                                 pcs_extent_summary* ext, pcs_extent* runs, uint64_t run_cap) {
+    if (!summary) return fail(PCS_ERR_INVALID, "summary is null");
+    if (!ext) return fail(PCS_ERR_INVALID, "ext is null");
+    if (corrupt_cap && !corrupt) return fail(PCS_ERR_INVALID, "corrupt is null with corrupt_cap > 0");
+    if (run_cap && !runs) return fail(PCS_ERR_INVALID, "runs is null with run_cap > 0");
+    if (injected_failure()) return fail(PCS_ERR_HIP, "injected failure (PCS_TUNE_FAIL_INJECT)");
+    return host_scrub(pages, page_size, n_pages, cls, type, summary, corrupt, corrupt_cap, ext, runs, run_cap);
 }
 
 int pcs_pages_stamp_dev(void* d_pages, uint64_t page_size, uint64_t n_pages, int algo, pcs_stream_t stream) {

@@ -1447,6 +1447,218 @@ __global__ __launch_bounds__(256) void k_scrub_list(const uint8_t* __restrict__ 
     }
 }
 
+// ---------------------------------------------------------------------------
+// Scrub extents (pcs_scrub_extents_dev): the maximal runs of equal class byte
+// as (first page, pages, class), ascending and capped, and the summary of the
+// written extent, the blank tail and the holes, from class bytes alone (any
+// sub-range of a scrub's, at any byte alignment).  The scrub reduction's
+// shape again, three launches ordered by construction:
+//   k_extent_count  one block per kScrubSpan pages: a page starts a run when
+//                   its byte differs from the byte before it (read from
+//                   memory, also across lanes and spans; page 0 always); the
+//                   span's run starts, blank-run starts, blank pages, first
+//                   run start, first blank-run start and last non-blank page
+//                   into a record;
+//   k_extent_scan   one block: exclusive scan of the records' run starts
+//                   (each span's rank in the list), an exclusive suffix
+//                   minimum of the spans' first run starts (where the run
+//                   that is open at a span's end stops), the summary;
+//   k_extent_emit   one block per span again: the spans whose rank is below
+//                   the cap write their runs at rank + position; a run's
+//                   length is the distance to the next start in the lane, in
+//                   the span's later lanes or in a later span, so a listed
+//                   run is whole whatever the cap.
+// ---------------------------------------------------------------------------
+constexpr int kExtentRec = 6;           // u32 per record: starts, blank starts, blank pages, first start, first blank start, last non-blank + 1
+constexpr int kExtentWords = 12;        // pcs_extent_summary
+constexpr int kExtentRunWords = 3;      // pcs_extent: first_page, n_pages, cls | reserved << 32
+constexpr uint32_t kExtentNone = 0xFFFFFFFFu;
+
+// Exclusive suffix minimum of v over a 256-thread block (the minimum over the
+// threads after this one, ~0 for the last; w4 as for block_excl_scan); all
+// receives the block minimum.
+__device__ __forceinline__ uint64_t block_excl_suffix_min(uint64_t v, uint64_t* w4, uint64_t& all) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint64_t incl = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t t = __shfl_down((unsigned long long)incl, d, 64);
+        if (lane + d < 64 && t < incl) incl = t;
+    }
+    const uint64_t next = __shfl_down((unsigned long long)incl, 1, 64);
+    if (lane == 0) w4[wave] = incl;
+    __syncthreads();
+    uint64_t after = lane < 63 ? next : ~0ull;
+    all = ~0ull;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const uint64_t x = w4[w];
+        if (w > wave && x < after) after = x;
+        if (x < all) all = x;
+    }
+    return after;
+}
+
+// This lane's 16 class bytes at page p0 < n: bit k of `starts` when page
+// p0 + k starts a run, bit k of `blank` when it is blank, `valid` = the bits
+// of the pages below n.
+__device__ __forceinline__ void extent_masks(const uint8_t* __restrict__ cls, uint64_t n, uint64_t p0, uint32_t& starts,
+                                             uint32_t& blank, uint32_t& valid) {
+    const uint64_t cnt = n - p0;
+    uint64_t cl, ch;
+    ld_bytes16(cls + p0, cnt, 0xFF, cl, ch);
+    valid = cnt >= 16 ? 0xFFFFu : (1u << cnt) - 1u;
+    uint32_t prev = p0 ? cls[p0 - 1] : 0x100u;  // no byte equals 0x100: page 0 always starts a run
+    starts = blank = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const uint32_t c = byte_of(cl, ch, k);
+        starts |= (c != prev ? 1u : 0u) << k;
+        blank |= (c == kClassBlank ? 1u : 0u) << k;
+        prev = c;
+    }
+    starts &= valid;
+    blank &= valid;
+}
+
+__global__ __launch_bounds__(256) void k_extent_count(const uint8_t* __restrict__ cls, uint64_t n,
+                                                     uint32_t* __restrict__ rec) {
+    __shared__ uint32_t cnt[kExtentRec];
+    if (threadIdx.x < kExtentRec) cnt[threadIdx.x] = (threadIdx.x == 3 || threadIdx.x == 4) ? kExtentNone : 0u;
+    __syncthreads();
+    const uint64_t p0 = (uint64_t)blockIdx.x * kScrubSpan + threadIdx.x * 16u;
+    uint64_t pack = 0;  // three 16-bit counters (a wave adds up to 1024 each): starts, blank starts, blank pages
+    uint32_t first = kExtentNone, first_blank = kExtentNone, last_written = 0;
+    if (p0 < n) {
+        uint32_t starts, blank, valid;
+        extent_masks(cls, n, p0, starts, blank, valid);
+        pack = (uint64_t)__builtin_popcount(starts) | (uint64_t)__builtin_popcount(starts & blank) << 16 |
+               (uint64_t)__builtin_popcount(blank) << 32;
+        if (starts) first = threadIdx.x * 16u + __builtin_ctz(starts);
+        if (starts & blank) first_blank = threadIdx.x * 16u + __builtin_ctz(starts & blank);
+        if (const uint32_t w = valid & ~blank) last_written = threadIdx.x * 16u + (32 - __builtin_clz(w));
+    }
+    const uint64_t sum = wave_sum(pack);
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int f = 0; f < 3; ++f)
+            if (const uint32_t x = (uint32_t)(sum >> (16 * f)) & 0xFFFF) atomicAdd(&cnt[f], x);
+    }
+    if (first != kExtentNone) atomicMin(&cnt[3], first);
+    if (first_blank != kExtentNone) atomicMin(&cnt[4], first_blank);
+    if (last_written) atomicMax(&cnt[5], last_written);
+    __syncthreads();
+    if (threadIdx.x < kExtentRec) rec[(uint64_t)blockIdx.x * kExtentRec + threadIdx.x] = cnt[threadIdx.x];
+}
+
+__global__ __launch_bounds__(256) void k_extent_scan(const uint8_t* __restrict__ cls, const uint32_t* __restrict__ rec,
+                                                    uint64_t nblocks, uint64_t n, uint64_t cap,
+                                                    uint64_t* __restrict__ rank, uint64_t* __restrict__ next,
+                                                    uint64_t* __restrict__ summary) {
+    __shared__ uint64_t w4[4];
+    __shared__ unsigned long long tot[4];  // blank runs, blank pages, first blank, written pages
+    if (threadIdx.x < 4) tot[threadIdx.x] = threadIdx.x == 2 ? ~0ull : 0ull;
+    __syncthreads();
+    uint64_t runs = 0;  // run starts in the spans before this round (uniform)
+    uint64_t blank_runs = 0, blank_pages = 0, first_blank = ~0ull, written = 0;  // this thread's spans
+    for (uint64_t base = 0; base < nblocks; base += 256) {
+        const uint64_t b = base + threadIdx.x;
+        uint64_t c = 0;
+        if (b < nblocks) {
+            const uint32_t* r = rec + b * kExtentRec;
+            c = r[0];
+            blank_runs += r[1];
+            blank_pages += r[2];
+            if (r[4] != kExtentNone && first_blank == ~0ull) first_blank = b * kScrubSpan + r[4];
+            if (r[5]) written = b * kScrubSpan + r[5];
+        }
+        uint64_t total;
+        const uint64_t before = block_excl_scan(c, w4, total);
+        if (b < nblocks) rank[b] = runs + before;
+        runs += total;
+        __syncthreads();
+    }
+    // next[b] = the first run start in the spans after b, n when there is none
+    uint64_t carry = n;
+    for (uint64_t base = (nblocks + 255) / 256 * 256; base != 0;) {
+        base -= 256;
+        const uint64_t b = base + threadIdx.x;
+        uint64_t v = ~0ull;
+        if (b < nblocks) {
+            const uint32_t f = rec[b * kExtentRec + 3];
+            if (f != kExtentNone) v = b * kScrubSpan + f;
+        }
+        uint64_t all;
+        const uint64_t after = block_excl_suffix_min(v, w4, all);
+        if (b < nblocks) next[b] = after < carry ? after : carry;
+        if (all < carry) carry = all;
+        __syncthreads();
+    }
+    const uint64_t a = wave_sum(blank_runs), p = wave_sum(blank_pages);
+    if ((threadIdx.x & 63) == 0) {
+        if (a) atomicAdd(&tot[0], (unsigned long long)a);
+        if (p) atomicAdd(&tot[1], (unsigned long long)p);
+    }
+    if (first_blank != ~0ull) atomicMin(&tot[2], (unsigned long long)first_blank);
+    if (written) atomicMax(&tot[3], (unsigned long long)written);
+    __syncthreads();
+    if (threadIdx.x < kExtentWords) {
+        const uint64_t n_blank_runs = tot[0], n_blank = tot[1], first = tot[2], w = tot[3];
+        const uint64_t last = n ? cls[n - 1] : ~0ull;
+        // every blank run but the tail (the one that starts at w) lies below w
+        const uint64_t holes = n_blank_runs - (last == kClassBlank ? 1 : 0);
+        uint64_t v = 0;
+        switch (threadIdx.x) {
+            case 0: v = n; break;
+            case 1: v = runs; break;
+            case 2: v = runs < cap ? runs : cap; break;
+            case 3: v = w; break;
+            case 4: v = n_blank; break;
+            case 5: v = n_blank_runs; break;
+            case 6: v = first; break;
+            case 7: v = holes; break;
+            case 8: v = n_blank - (n - w); break;
+            case 9: v = holes ? first : ~0ull; break;
+            case 10: v = n ? cls[0] : ~0ull; break;
+            default: v = last; break;
+        }
+        summary[threadIdx.x] = v;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_extent_emit(const uint8_t* __restrict__ cls, uint64_t n,
+                                                    const uint32_t* __restrict__ rec,
+                                                    const uint64_t* __restrict__ rank,
+                                                    const uint64_t* __restrict__ next, uint64_t cap,
+                                                    uint64_t* __restrict__ runs) {
+    __shared__ uint64_t w4[4];
+    const uint64_t r0 = rank[blockIdx.x];
+    if (rec[(uint64_t)blockIdx.x * kExtentRec] == 0 || r0 >= cap) return;  // uniform over the block
+    const uint64_t p0 = (uint64_t)blockIdx.x * kScrubSpan + threadIdx.x * 16u;
+    uint32_t starts = 0, blank, valid;
+    uint64_t cl = 0, ch = 0;
+    if (p0 < n) {
+        extent_masks(cls, n, p0, starts, blank, valid);
+        ld_bytes16(cls + p0, n - p0, 0xFF, cl, ch);
+    }
+    uint64_t total, all;
+    uint64_t pos = r0 + block_excl_scan(__builtin_popcount(starts), w4, total);
+    __syncthreads();
+    // where the last run that starts in this lane ends: the next start in the span's later lanes, or after the span
+    uint64_t end = block_excl_suffix_min(starts ? p0 + __builtin_ctz(starts) : ~0ull, w4, all);
+    const uint64_t after = next[blockIdx.x];
+    if (after < end) end = after;
+    while (starts && pos < cap) {
+        const int k = __builtin_ctz(starts);
+        starts &= starts - 1;
+        const uint64_t stop = starts ? p0 + __builtin_ctz(starts) : end;
+        uint64_t* r = runs + pos++ * kExtentRunWords;
+        r[0] = p0 + k;
+        r[1] = stop - (p0 + k);
+        r[2] = byte_of(cl, ch, k);
+    }
+}
+
 // Streaming-read ceiling, built on k_xxh3_fixed<4096>'s exact
 // structure (round 5's 64 KiB-window reader ran ~4 % below
 // the hash kernel it was meant to bound): 256-thread blocks of 16 four-KiB
@@ -1947,6 +2159,34 @@ hipError_t run_scrub(const uint8_t* pages, uint64_t P, uint64_t n, uint8_t* cls,
     hipError_t e = hipGetLastError();
     if (e == hipSuccess && n && cap) {
         hipLaunchKernelGGL(k_scrub_list, dim3((unsigned)nblocks), dim3(256), 0, s, cls, n, rec, rank, cap, list);
+        e = hipGetLastError();
+    }
+    return e;
+}
+
+// Extents of n class bytes: summary and the first min(runs, cap) runs.  Reads
+// cls only; nothing here waits for the stream; n == 0 still writes the whole
+// summary.
+hipError_t run_extents(const uint8_t* cls, uint64_t n, uint64_t* summary, uint64_t* runs, uint64_t cap,
+                       hipStream_t s) {
+    const uint64_t nblocks = (n + kScrubSpan - 1) / kScrubSpan;
+    if (nblocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    ScratchLease scratch(s);  // ranks, next starts and records
+    uint64_t *rank = nullptr, *next = nullptr;
+    uint32_t* rec = nullptr;
+    if (n) {
+        hipError_t e = scratch.get(nblocks * (16 + kExtentRec * 4));
+        if (e != hipSuccess) return e;
+        rank = static_cast<uint64_t*>(scratch.p);
+        next = rank + nblocks;
+        rec = reinterpret_cast<uint32_t*>(next + nblocks);
+        hipLaunchKernelGGL(k_extent_count, dim3((unsigned)nblocks), dim3(256), 0, s, cls, n, rec);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_extent_scan, dim3(1), dim3(256), 0, s, cls, rec, nblocks, n, cap, rank, next, summary);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && n && cap) {
+        hipLaunchKernelGGL(k_extent_emit, dim3((unsigned)nblocks), dim3(256), 0, s, cls, n, rec, rank, next, cap, runs);
         e = hipGetLastError();
     }
     return e;

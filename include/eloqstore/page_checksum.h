@@ -124,6 +124,36 @@ int TryScrubPages(std::span<const char* const> pages, size_t page_size, ScrubRep
                   size_t max_listed = 1024);
 ScrubReport ScrubPages(std::span<const char* const> pages, size_t page_size, size_t max_listed = 1024);
 
+// Scrub extents (pcs_pages_scrub_extents_host): the scrub above without the
+// per-page arrays, plus where the classes lie: the maximal runs of equal class
+// (the first max_runs of them, ascending, each with its full length), the
+// written extent and the holes.  An append-mode data file is written in page
+// order, so a blank page below written_pages (a hole) is a lost or trimmed
+// write there; the blank pages from written_pages on are the never-written tail.
+struct PageExtent {
+    uint64_t first_page = 0, n_pages = 0;
+    uint8_t page_class = 0;  // pcs_page_class
+};
+struct ExtentReport {
+    uint64_t n_pages = 0, n_ok = 0, n_corrupt = 0, n_blank = 0;
+    uint64_t ok_by_type[6] = {};       // as ScrubReport
+    uint64_t first_corrupt = UINT64_MAX;
+    std::vector<uint64_t> corrupt;     // the smallest corrupt page indices, ascending, at most max_listed
+    uint64_t n_runs = 0;               // all runs, whatever max_runs
+    uint64_t written_pages = 0;        // 1 + the last non-blank page; 0 when every page is blank
+    uint64_t n_blank_runs = 0;         // the tail included
+    uint64_t first_blank = UINT64_MAX;
+    uint64_t n_holes = 0, n_hole_pages = 0;
+    uint64_t first_hole = UINT64_MAX;
+    std::vector<PageExtent> runs;      // the first min(n_runs, max_runs) runs
+};
+// PCS_OK or a negative pcs_status (message in LastChecksumError()); a failed
+// call leaves the report unspecified.
+int TryScrubExtents(std::span<const char* const> pages, size_t page_size, ExtentReport& report,
+                    size_t max_runs = 1024, size_t max_listed = 1024);
+ExtentReport ScrubExtents(std::span<const char* const> pages, size_t page_size, size_t max_runs = 1024,
+                          size_t max_listed = 1024);
+
 // Registers a page-pool chunk or io_uring buffer ring once (PagesPool::Extend,
 // src/storage/page.cpp:95-120): batches whose pages all lie in registered
 // memory are then hashed in place over PCIe in one launch, with no gather

@@ -97,7 +97,10 @@ enum pcs_flags {
  *      pcs_stream_read_dev writes
  *      one word per 4 KiB (was per 64 KiB: size d_out for the new count)
  *   7  page scrub: pcs_pages_scrub_dev / pcs_pages_scrub_host, enum
- *      pcs_page_class and struct pcs_scrub_summary; additive, no prototype changed */
+ *      pcs_page_class and struct pcs_scrub_summary; additive, no prototype changed.
+ *      Added later under the same number, additive again (detect them by
+ *      symbol): pcs_scrub_extents_dev / pcs_pages_scrub_extents_host, struct
+ *      pcs_extent and struct pcs_extent_summary */
 #define PCS_ABI_VERSION 7
 int pcs_abi_version(void);
 const char *pcs_version(void);
@@ -178,6 +181,65 @@ int pcs_pages_scrub_dev(const void *d_pages, uint64_t page_size, uint64_t n_page
 int pcs_pages_scrub_host(const void *const *pages, uint64_t page_size, uint64_t n_pages, uint8_t *cls,
                          uint8_t *type, pcs_scrub_summary *summary, uint64_t *corrupt,
                          uint64_t corrupt_cap);
+
+/* ---- scrub extents: class runs, written extent and holes --------------------
+ * A run-length view of a scrub's class bytes, computed on the device.  An
+ * append-mode data file is written strictly in page order, so its written
+ * pages form a prefix and its blank pages a suffix: a blank page BELOW the
+ * last written page is a lost or trimmed write, and a scrub that only counts
+ * blank pages cannot tell the two apart.
+ *
+ * A run is a maximal range of equal class bytes.  Only byte 2 (PCS_PAGE_BLANK)
+ * is blank and only byte 0 is corrupt; any other byte value is a class of its
+ * own kind: never blank, it splits runs by inequality and is reported as is in
+ * `cls`.  d_runs[0 .. n_listed) receives the first n_listed = min(n_runs,
+ * run_cap) runs in ascending order, each with its FULL length, also when it
+ * extends far beyond the pages the other listed runs cover; entries at n_listed
+ * and beyond are not written.  Every call writes the whole summary, whatever it
+ * held before; n_pages == 0 gives zero counts and UINT64_MAX in first_blank,
+ * first_hole, first_class and last_class.  The output is the same from call to
+ * call (no atomic append).
+ *
+ * pcs_scrub_extents_dev reads only d_class[0 .. n_pages), about one byte per
+ * page, never the pages: d_class is the class array a scrub wrote or any
+ * sub-range of it at any byte alignment (one device batch may hold several
+ * data files; take the extents per file).  It enqueues on `stream` and never
+ * synchronises; its scratch is event-fenced per stream.  d_runs may be NULL
+ * iff run_cap == 0 (the list pass is then skipped).
+ *
+ * pcs_pages_scrub_extents_host is pcs_pages_scrub_host (same pipeline, page
+ * size rule, summary, corrupt list, PCS_TUNE_FAIL_INJECT and errors) that also
+ * takes the extents of every 32 MiB chunk while its class bytes are still on
+ * the device, and merges the chunks into global page indices: a run that
+ * crosses a chunk edge is one run, and one chunk's blank tail is a hole as soon
+ * as a later chunk holds a non-blank page, so the result is that of one pass
+ * over the whole class array.  Here cls and type may both be NULL: a caller
+ * that scrubs a whole store then allocates nothing per page.  summary and ext
+ * must be non-NULL; runs may be NULL iff run_cap == 0. */
+typedef struct pcs_extent {
+    uint64_t first_page, n_pages;
+    uint32_t cls;      /* the class byte of the run's pages */
+    uint32_t reserved; /* 0 */
+} pcs_extent;
+typedef struct pcs_extent_summary { /* 12 x u64, the same layout on device and host */
+    uint64_t n_pages;
+    uint64_t n_runs;        /* all maximal runs, whatever the cap */
+    uint64_t n_listed;      /* min(n_runs, run_cap) */
+    uint64_t written_pages; /* 1 + index of the last non-blank page; 0 when every page is blank */
+    uint64_t n_blank;       /* blank pages */
+    uint64_t n_blank_runs;  /* blank runs, the tail included */
+    uint64_t first_blank;   /* first blank page, UINT64_MAX when none */
+    uint64_t n_holes;       /* blank runs that start below written_pages */
+    uint64_t n_hole_pages;  /* blank pages below written_pages */
+    uint64_t first_hole;    /* first page of the first hole, UINT64_MAX when none */
+    uint64_t first_class, last_class; /* class byte of page 0 / page n-1; UINT64_MAX when n_pages == 0 */
+} pcs_extent_summary;
+int pcs_scrub_extents_dev(const uint8_t *d_class, uint64_t n_pages, pcs_extent_summary *d_summary,
+                          pcs_extent *d_runs, uint64_t run_cap, pcs_stream_t stream);
+int pcs_pages_scrub_extents_host(const void *const *pages, uint64_t page_size, uint64_t n_pages,
+                                 uint8_t *cls, uint8_t *type, pcs_scrub_summary *summary,
+                                 uint64_t *corrupt, uint64_t corrupt_cap, pcs_extent_summary *ext,
+                                 pcs_extent *runs, uint64_t run_cap);
 
 /* ---- device-resident descriptor batches (mixed page sizes) ----------------
  * Page i occupies [d_base + d_off[i], d_base + d_off[i] + d_len[i]).  Pages

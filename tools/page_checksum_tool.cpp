@@ -21,6 +21,13 @@
 //       data file), count the ok pages by PageType and list up to 64
 //       corrupted offsets.  Exit 2 if any page is corrupted; blank pages do
 //       not fail a scrub (--scan counts them as corrupted).
+//   page_checksum_tool --extents <file_path> [page_size]   --scrub's counts, then
+//       where the classes lie: the written extent (pages [0, W), W = 1 + the
+//       last non-blank page) and the blank tail behind it, the holes (blank
+//       runs below W) and up to 64 corrupted extents as offset and length.
+//       Exit 2 if any page is corrupted, else 3 if there is a hole, else 0.
+//       An append-mode data file is written in page order, so only there does
+//       a hole (exit 3) mean a lost or trimmed write.
 //   --scan/--stamp print a summary line with the GiB/s of the call; exit codes
 //   as above (--scan: 2 if any page is corrupted).
 #include <fcntl.h>
@@ -40,6 +47,8 @@
 
 #include "eloqstore/page_checksum.h"
 #include "eloqstore_pcs.h"
+#include "extent_merge.h"
+#include "scrub_merge.h"
 
 namespace {
 
@@ -62,8 +71,11 @@ void usage(const char* prog) {
                  "Offset and page size accept decimal or 0x-prefixed hex values.\n"
                  "       %s --scan|--stamp <file_path> [page_size_bytes]\n"
                  "       %s --scrub <file_path> [page_size_bytes]\n"
+                 "       %s --extents <file_path> [page_size_bytes]\n"
+                 "           exit 2: corrupted pages; exit 3: a blank page below the last written one\n"
+                 "           (a lost write only for append-mode files, which are written in page order)\n"
                  "       %s --gen <file_path> <n_pages> [page_size_bytes] [seed]\n",
-                 prog, prog, prog, prog);
+                 prog, prog, prog, prog, prog);
 }
 
 constexpr uint64_t kDefaultPageSize = 4096;  // KvOptions{}.data_page_size
@@ -284,8 +296,13 @@ int bulk(bool stamp, const char* path, const char* size_s) {
 // chunk k.  Never-written (all-zero) pages are counted, not failed; the first
 // kScrubLines corrupted pages are listed by offset.
 constexpr uint64_t kScrubLines = 64;
+// --extents: the same loop with pcs_pages_scrub_extents_host per file chunk
+// (no per-page array comes back) and the file chunks merged by ScrubMerge and
+// ExtentMerge.  The corrupted extents printed are those among the first
+// kExtentRuns runs of the file.
+constexpr uint64_t kExtentRuns = 1024;
 
-int scrub(const char* path, const char* size_s) {
+int scrub(const char* path, const char* size_s, bool extents = false) {
     uint64_t P = kDefaultPageSize;
     if (size_s && (!parse_u64(size_s, P) || P < 249 || P > 0xFFFFFFFFull)) {
         std::fprintf(stderr, "Invalid page size: %s (scrub needs 249 <= page size < 2^32)\n", size_s);
@@ -317,6 +334,13 @@ int scrub(const char* path, const char* size_s) {
     pcs_scrub_summary total{}, part{};
     total.first_corrupt = UINT64_MAX;
     uint64_t listed[kScrubLines];
+    // --extents only
+    pcs_scrub_summary ex_total;
+    pcs_extent_summary ext_total, ext_part{};
+    std::vector<pcs_extent> runs(extents ? kExtentRuns : 0), part_runs;
+    pcs::ScrubMerge scrub_merge(&ex_total, listed, kScrubLines);
+    pcs::ExtentMerge extent_merge(&ext_total, runs.data(), runs.size());
+    uint64_t part_listed[kScrubLines];
     {
         // warm the GPU path before the clock starts, as --scan does
         std::memset(buf[0], 0, (size_t)P);
@@ -343,7 +367,16 @@ int scrub(const char* path, const char* size_s) {
         const char* b = static_cast<const char*>(buf[s]);
         for (uint64_t i = 0; i < cnt; ++i) ptrs[i] = b + i * P;
         const uint64_t room = kScrubLines - total.n_listed;
-        if (pcs_pages_scrub_host(ptrs.data(), P, cnt, cls.data(), nullptr, &part, room ? listed + total.n_listed : nullptr,
+        if (extents) {
+            part_runs.resize(pcs::ExtentMerge::chunk_cap(runs.size(), cnt));
+            if (pcs_pages_scrub_extents_host(ptrs.data(), P, cnt, nullptr, nullptr, &part, part_listed, kScrubLines,
+                                             &ext_part, part_runs.data(), part_runs.size())) {
+                rc = 1;
+            } else {
+                scrub_merge.add(part, part_listed, p0);
+                extent_merge.add(ext_part, part_runs.data(), p0);
+            }
+        } else if (pcs_pages_scrub_host(ptrs.data(), P, cnt, cls.data(), nullptr, &part, room ? listed + total.n_listed : nullptr,
                                  room)) {
             rc = 1;
         } else {
@@ -364,6 +397,7 @@ int scrub(const char* path, const char* size_s) {
         std::fprintf(stderr, "scrub failed: %s\n", pcs_last_error());
         return 1;
     }
+    if (extents) total = ex_total;
     const double gib = (double)(n * P) / (1024.0 * 1024.0 * 1024.0);
     std::printf("Scrubbed %llu pages of %llu bytes: %llu ok, %llu corrupted, %llu blank (%.3f s, %.2f GiB/s incl. file I/O)\n",
                 (unsigned long long)n, (unsigned long long)P, (unsigned long long)total.n_ok,
@@ -372,6 +406,28 @@ int scrub(const char* path, const char* size_s) {
                 (unsigned long long)total.ok_by_type[0], (unsigned long long)total.ok_by_type[1],
                 (unsigned long long)total.ok_by_type[2], (unsigned long long)total.ok_by_type[3],
                 (unsigned long long)total.ok_by_type[4], (unsigned long long)total.ok_by_type[5]);
+    if (extents) {
+        const pcs_extent_summary& e = ext_total;
+        std::printf("written extent: pages [0, %llu) of %llu, blank tail: %llu pages\n",
+                    (unsigned long long)e.written_pages, (unsigned long long)e.n_pages,
+                    (unsigned long long)(e.n_pages - e.written_pages));
+        if (e.n_holes)
+            std::printf("holes: %llu (%llu pages), first at offset %llu\n", (unsigned long long)e.n_holes,
+                        (unsigned long long)e.n_hole_pages, (unsigned long long)(e.first_hole * P));
+        else
+            std::printf("holes: none\n");
+        uint64_t lines = 0, shown = 0;
+        for (uint64_t i = 0; i < e.n_listed && lines < kScrubLines; ++i) {
+            if (runs[i].cls != PCS_PAGE_CORRUPT) continue;
+            std::printf("corrupted extent at offset %llu: %llu pages\n", (unsigned long long)(runs[i].first_page * P),
+                        (unsigned long long)runs[i].n_pages);
+            ++lines;
+            shown += runs[i].n_pages;
+        }
+        if (total.n_corrupt > shown)
+            std::printf("... and %llu more corrupted pages\n", (unsigned long long)(total.n_corrupt - shown));
+        return total.n_corrupt ? 2 : e.n_holes ? 3 : 0;
+    }
     for (uint64_t i = 0; i < total.n_listed; ++i)
         std::printf("corrupted page at offset %llu\n", (unsigned long long)(listed[i] * P));
     if (total.n_corrupt > kScrubLines)
@@ -419,12 +475,12 @@ int main(int argc, char** argv) {
         }
         return bulk(argv[1][2] == 's' && argv[1][3] == 't', argv[2], argc == 4 ? argv[3] : nullptr);
     }
-    if (argc >= 2 && !std::strcmp(argv[1], "--scrub")) {
+    if (argc >= 2 && (!std::strcmp(argv[1], "--scrub") || !std::strcmp(argv[1], "--extents"))) {
         if (argc < 3 || argc > 4) {
             usage(argv[0]);
             return 1;
         }
-        return scrub(argv[2], argc == 4 ? argv[3] : nullptr);
+        return scrub(argv[2], argc == 4 ? argv[3] : nullptr, argv[1][2] == 'e');
     }
     if (argc >= 2 && !std::strcmp(argv[1], "--gen")) {
         if (argc < 4 || argc > 6) {
