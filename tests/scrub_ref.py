@@ -70,6 +70,81 @@ def near_blank_offsets(P: int):
     return sorted({o for o in offs if 0 <= o < P})
 
 
+WALK_FULL_MAX = 5120     # every byte of a page is walked up to this size
+WALK_PIECE_MAX = 65536   # one byte per 16-byte piece up to this size, one per 64-byte stripe above
+WALK_ENDS = 1100         # every byte of the first and the last WALK_ENDS bytes
+WALK_EDGE = 24           # every byte within WALK_EDGE of a multiple of 4096 (slice and 4-block batch edges)
+WALK_CONTROL_EVERY = 17  # rows 0, 17, 34, ... are control pages: 17 j % 16 = j % 16, every group slot of a tile
+CONTROL_KINDS = ("blank", "zero_body_ok", "random_ok", "header_bit")
+
+
+def walk_offsets(P: int) -> np.ndarray:
+    """The byte offsets a walk batch visits, ascending (int64).
+
+    P <= 5120: every byte.  Up to 64 KiB: one byte in every 16-byte piece k,
+    16k + (5k + k // 16) % 16 (over 256 consecutive pieces that is every
+    (lane, byte-in-piece) and every (chunk, byte-in-piece) pair), every byte of
+    the first and last 1100, and every byte within 24 of a multiple of 4096.
+    Above: one byte in every 64-byte stripe s, 64s + (13s + s // 16) % 64, and
+    the two 1100-byte ends."""
+    if P <= WALK_FULL_MAX:
+        return np.arange(P, dtype=np.int64)
+    ends = np.concatenate((np.arange(0, WALK_ENDS), np.arange(P - WALK_ENDS, P)))
+    if P <= WALK_PIECE_MAX:
+        k = np.arange((P + 15) // 16, dtype=np.int64)
+        one = 16 * k + (5 * k + k // 16) % 16
+        m = np.arange(0, P + 1, 4096, dtype=np.int64)
+        edges = (m[:, None] + np.arange(-WALK_EDGE, WALK_EDGE + 1)).ravel()
+        offs = np.concatenate((one, ends, edges))
+    else:
+        s = np.arange((P + 63) // 64, dtype=np.int64)
+        one = 64 * s + (13 * s + s // 16) % 64
+        offs = np.concatenate((one, ends))
+    offs = np.minimum(offs, P - 1)
+    return np.unique(offs[offs >= 0]).astype(np.int64)
+
+
+def walk_bit(offs) -> np.ndarray:
+    """The one set bit a walk page carries at offset o."""
+    o = np.asarray(offs, dtype=np.int64)
+    return (np.uint8(1) << ((o + o // 16) % 8).astype(np.uint8)).astype(np.uint8)
+
+
+def build_walk_batch(P: int, seed: int = 1):
+    """One walk page per offset of walk_offsets(P): all zero but for one byte
+    holding the single bit walk_bit(o).  Rows 0, 17, 34, ... are control pages
+    of the four CONTROL_KINDS in turn (control j is kind j % 4): blank; a zero
+    body under its correct stamped header; a random stamped page with a type
+    byte of TYPE_BYTES; a zero body under a header with the one bit j % 64 set.
+    A blank control page is appended, so the first and the last page are blank.
+    Returns (pages (n, P) uint8, rows): rows[kind] are the row indices of each
+    control kind, rows["offsets"] / rows["walk_rows"] the offsets and the rows
+    of their pages (aligned arrays), rows["walk"] the same as offset -> row."""
+    offs = walk_offsets(P)
+    nw = offs.size
+    E = WALK_CONTROL_EVERY
+    # walk page i sits at the i-th row that is not a multiple of 17
+    walk_rows = np.arange(nw, dtype=np.int64) + np.arange(nw, dtype=np.int64) // (E - 1) + 1
+    n = int(walk_rows[-1]) + 2
+    pg = np.zeros((n, P), dtype=np.uint8)
+    pg[walk_rows, offs] = walk_bit(offs)
+    ctl = np.arange(0, n - 1, E, dtype=np.int64)  # the appended page n - 1 is not among them
+    rows = {kind: ctl[i::4].tolist() for i, kind in enumerate(CONTROL_KINDS)}
+    rows["blank"].append(n - 1)
+    rng = np.random.default_rng(seed * 1000003 + P * 31)
+    rnd = np.asarray(rows["random_ok"], dtype=np.int64)
+    pg[rnd] = rng.integers(0, 256, size=(rnd.size, P), dtype=np.uint8)
+    pg[rnd, 8] = np.array(TYPE_BYTES, dtype=np.uint8)[(rnd // E // 4) % len(TYPE_BYTES)]
+    stamp(pg, rnd)
+    stamp(pg, rows["zero_body_ok"])
+    for r in rows["header_bit"]:
+        bit = (r // E) % 64
+        pg[r, bit // 8] = 1 << (bit % 8)
+    rows["offsets"], rows["walk_rows"] = offs, walk_rows
+    rows["walk"] = dict(zip(offs.tolist(), walk_rows.tolist()))
+    return pg, rows
+
+
 def build_batch(P: int, n: int, seed: int = 1, near=None, flips: int = 12, zero_header: bool = True):
     """A mixed batch of n pages: OK pages of all six type buckets (type byte
     set before stamping), `flips` pages corrupted by a flip at byte 10 (fewer

@@ -3,7 +3,9 @@ always against tests/scrub_ref.py: classes, type bytes, summary and the capped
 ascending corrupt list, on every XXH3 page kernel family (fixed, split,
 any-size stride, the unaligned run-time body), with outputs pre-filled with
 garbage, repeated calls, two streams, a 256 MiB batch (XCD tile remap,
-multi-block reduction) and the host pipeline across its 32 MiB chunk boundary.
+multi-block reduction) and the host pipeline across its 32 MiB chunk boundary,
+at 4 KiB and at page sizes off the 256-byte grid (1000 gathered, 5000 direct
+DMA; with the extents form).  The call helpers are in tests/scrub_gpu.py.
 
 Every batch mixes OK pages of all six type buckets, flipped pages, blank
 pages (page 0, page n - 1, a whole 16-page tile), a zero header over a
@@ -21,12 +23,12 @@ import pytest
 import torch
 
 import eloqstore_amd as pcs
+import extent_ref
 import scrub_ref
+from scrub_gpu import DEV, garbage, scrub_checked, to_dev
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 HERE = os.path.dirname(os.path.abspath(__file__))
-SENTINEL = 0x5A5A5A5A5A5A5A5A
 
 # fixed; split (8, 16, 64 KiB); any-size stride; plus one multiple of 256 that is no compiled size
 SHAPES = [(4096, 1003), (8192, 203), (16384, 101), (65536, 37), (249, 100), (1000, 517), (5000, 333), (2560, 77)]
@@ -51,43 +53,6 @@ def check_batch_on_cpu(pg, rows, P):
     assert all(cls[r] == scrub_ref.CORRUPT for r in rows["near_blank"].values())
     assert (cls[rows["flipped"]] == scrub_ref.CORRUPT).all()
     return cls, types, s, bad
-
-
-def to_dev(pg, offset=0):
-    flat = torch.from_numpy(np.ascontiguousarray(pg).reshape(-1))
-    buf = torch.empty(flat.numel() + 16, dtype=torch.uint8, device=DEV)
-    view = buf[offset: offset + flat.numel()]
-    view.copy_(flat)
-    return view
-
-
-def garbage(n, cap):
-    return (torch.full((max(n, 1),), 0xEE, dtype=torch.uint8, device=DEV)[:n],
-            torch.full((max(n, 1),), 0xDD, dtype=torch.uint8, device=DEV)[:n],
-            torch.full((12,), 0x1234567, dtype=torch.int64, device=DEV),
-            torch.from_numpy(np.full(max(cap, 1), SENTINEL, dtype=np.uint64).view(np.int64)).to(DEV))
-
-
-def scrub_checked(dpages, P, n, want, cap=1024, reps=3, types=True):
-    """reps calls into garbage-filled outputs, each compared with `want`."""
-    wcls, wtypes, ws, wbad = want
-    for _ in range(reps):
-        cls, ty, summ, lst = garbage(n, cap)
-        pcs.pages_scrub_async(dpages, P, n, cls, ty if types else False, summ, lst if cap else None, cap)
-        torch.cuda.synchronize()
-        got = pcs.summary_dict(summ.cpu().tolist())
-        ws_cap = dict(ws, n_listed=min(ws["n_corrupt"], cap))
-        assert got == ws_cap, (got, ws_cap)
-        assert np.array_equal(cls.cpu().numpy(), wcls)
-        if types:
-            assert np.array_equal(ty.cpu().numpy(), wtypes)
-        else:
-            assert (ty.cpu().numpy() == 0xDD).all()  # a NULL type array leaves the caller's memory alone
-        l = lst.cpu().numpy().view(np.uint64)
-        k = got["n_listed"]
-        assert np.array_equal(l[:k], wbad[:k])
-        assert (l[k:] == SENTINEL).all()  # entries at n_listed and beyond are not written
-    return cls
 
 
 @pytest.mark.parametrize("P,n", SHAPES)
@@ -172,7 +137,7 @@ def test_two_streams_interleaved():
     for k, (P, n, d, (wcls, wtypes, ws, wbad)) in enumerate(work):
         for cls, ty, summ, lst in outs[k]:
             assert pcs.summary_dict(summ.cpu().tolist()) == ws
-            assert np.array_equal(cls.cpu().numpy(), wcls) and np.array_equal(ty.cpu().numpy(), wtypes)
+            assert np.array_equal(cls.cpu().numpy()[:n], wcls) and np.array_equal(ty.cpu().numpy()[:n], wtypes)
             assert np.array_equal(lst.cpu().numpy().view(np.uint64)[:9], wbad)
 
 
@@ -241,6 +206,105 @@ def test_host_form_direct_dma_across_the_chunk_boundary():
         assert s == ws, (cap, s, ws)
         assert np.array_equal(lst, wbad) and np.array_equal(lst, bad[:cap].astype(np.uint64))
         assert np.array_equal(cls, wcls) and np.array_equal(types, wtypes)
+
+
+STAGE_BYTES = 32 << 20  # pcs_capi.cpp kStageBytes: a chunk of the staged pipeline holds STAGE_BYTES // P pages
+EDGE_NEAR = (0, 8, 999, 500)
+
+
+def offgrid_batch(P, seed):
+    """STAGE_BYTES // P + 700 stamped pages of every type bucket with blank,
+    near-blank (one byte 0x01 at each of EDGE_NEAR) and flipped pages just
+    before and just after page e = STAGE_BYTES // P, the first page of the
+    second chunk.  -> (pages, e, spare): page e itself is left to the caller,
+    spare is a copy of its stamped content."""
+    e = STAGE_BYTES // P
+    n = e + 700
+    rng = np.random.default_rng(seed)
+    pg = rng.integers(0, 256, size=(n, P), dtype=np.uint8)
+    pg[:, 8] = np.array(scrub_ref.TYPE_BYTES, dtype=np.uint8)[np.arange(n) % 6]
+    scrub_ref.stamp(pg, np.arange(n))
+    spare = pg[e].copy()
+    for side in (e - 6, e + 3):
+        for j, off in enumerate(EDGE_NEAR):
+            pg[side + j] = 0
+            pg[side + j, off] = 1
+    pg[[0, e - 2, e + 1, n - 1]] = 0
+    pg[[5, e - 1, e + 2, n - 2], 10] ^= 0xFF
+    return pg, e, spare
+
+
+def check_host_forms(ptrs, wcls, wtypes, P, counter, chunks):
+    """pcs.scrub_ptrs and pcs.scrub_extents_ptrs against the reference classes
+    of the same pages; each call moves `counter` by `chunks`."""
+    for cap, run_cap in ((1024, 1024), (7, 5)):
+        ws, wbad = scrub_ref.summarize(wcls, wtypes, cap)
+        we, wruns = extent_ref.extents(wcls, run_cap=run_cap)
+        before = pcs.counter(counter)
+        cls, types, s, bad = pcs.scrub_ptrs(ptrs, P, corrupt_cap=cap)
+        assert pcs.counter(counter) == before + chunks
+        assert s == ws, (s, ws)
+        assert np.array_equal(bad, wbad) and np.array_equal(cls, wcls) and np.array_equal(types, wtypes)
+        before = pcs.counter(counter)
+        s, bad, e, runs, cls, types = pcs.scrub_extents_ptrs(ptrs, P, run_cap=run_cap, corrupt_cap=cap, per_page=True)
+        assert pcs.counter(counter) == before + chunks
+        assert s == ws and np.array_equal(bad, wbad) and np.array_equal(cls, wcls) and np.array_equal(types, wtypes)
+        assert e == we, (e, we)
+        for f in ("first_page", "n_pages", "cls"):
+            assert np.array_equal(runs[f], wruns[f]), f
+    s, bad, e, runs = pcs.scrub_extents_ptrs(ptrs, P, run_cap=1024, corrupt_cap=1024)  # NULL cls / type
+    assert s == scrub_ref.summarize(wcls, wtypes, 1024)[0] and e == extent_ref.extents(wcls, run_cap=1024)[0]
+
+
+def edge_page_variants(pg, e, spare):
+    """Page e blank, near-blank at its last byte, and flipped, in turn."""
+    pg[e] = 0
+    yield "blank"
+    pg[e, -1] = 1
+    yield "near-blank"
+    pg[e] = spare
+    pg[e, 10] ^= 0xFF
+    yield "flipped"
+
+
+def edge_reference(pg, P, e, what):
+    """Reference classes and types; the batch holds what it should around page e."""
+    wcls, wtypes, _, _ = scrub_ref.classify(pg, P)
+    assert wcls[e] == (scrub_ref.BLANK if what == "blank" else scrub_ref.CORRUPT), what
+    assert wcls[0] == wcls[e - 2] == wcls[e + 1] == wcls[-1] == scrub_ref.BLANK
+    assert (wcls[[e - 6, e - 5, e - 4, e - 3, e - 1, e + 2, e + 3, e + 4, e + 5, e + 6]] == scrub_ref.CORRUPT).all()
+    assert wcls[e - 7] == wcls[e + 7] == scrub_ref.OK
+    return wcls, wtypes
+
+
+def test_host_forms_gather_off_grid_pages_across_the_chunk_edge():
+    """P = 1000 (the any-size body), 33,554 pages per chunk: scattered pages,
+    two gathered chunks."""
+    P = 1000
+    pg, e, spare = offgrid_batch(P, 0x0FF1)
+    n = len(pg)
+    assert e == 33554 and n == 33554 + 700
+    order = np.random.default_rng(7).permutation(n)
+    store = np.empty((n, P), dtype=np.uint8)
+    ptrs = np.uint64(store.ctypes.data) + order.astype(np.uint64) * np.uint64(P)  # page i lives in row order[i]
+    for what in edge_page_variants(pg, e, spare):
+        store[order] = pg
+        check_host_forms(ptrs, *edge_reference(pg, P, e, what), P, pcs.COUNTER_GATHER_CHUNKS, 2)
+
+
+def test_host_forms_direct_dma_off_grid_pages_across_the_chunk_edge():
+    """P = 5000, 6,710 pages per chunk, one contiguous pinned buffer: two
+    chunks on the direct DMA path."""
+    P = 5000
+    pg, e, spare = offgrid_batch(P, 0x0FF5)
+    n = len(pg)
+    assert e == 6710
+    pinned = torch.empty(n * P, dtype=torch.uint8, pin_memory=True)
+    view = pinned.numpy().reshape(n, P)
+    ptrs = np.arange(n, dtype=np.uint64) * np.uint64(P) + np.uint64(pinned.data_ptr())
+    for what in edge_page_variants(pg, e, spare):
+        view[:] = pg
+        check_host_forms(ptrs, *edge_reference(pg, P, e, what), P, pcs.COUNTER_DIRECT_DMA_CHUNKS, 2)
 
 
 def test_cli_scrub_tells_blank_from_corrupted(tmp_path):

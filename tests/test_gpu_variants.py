@@ -2,7 +2,7 @@
 bits.  The knobs pick between kernels and layouts (non-temporal loads, grid
 caps, XXH64 LDS depth and waves per workgroup, split pages, 4-block run-time
 batches); each must stay bit-exact with the oracle in digest, validate and
-stamp modes.  (Variants measured slower were retired in round 2: in-place
+stamp modes, and with tests/scrub_ref.py in scrub mode.  (Variants measured slower were retired in round 2: in-place
 stamp, XXH64 quad layout, descriptor slices / sorts; their keys now fail.)
 """
 import numpy as np
@@ -11,6 +11,8 @@ import torch
 
 import eloqstore_amd as pcs
 import oracle
+import scrub_gpu
+import scrub_ref
 from workload import mixed_layout
 
 pytestmark = pytest.mark.gpu
@@ -67,6 +69,35 @@ def test_variant_pages(tuned, P, n, algo):
     ok, fb = pcs.pages_validate(buf, P, n, algo)
     assert np.array_equal(np.flatnonzero(ok.cpu().numpy() == 0), np.arange(0, n, 9)), tuned
     assert int(fb.cpu().numpy().view(np.uint64)[0]) == 0
+
+
+SCRUB_SHAPES = [(4096, 1003), (16384, 101), (2560, 77)]  # fixed, split (fixed under no_split), run-time size
+
+
+@pytest.fixture(scope="module")
+def scrub_batches():
+    """Each shape's mixed batch (scrub_ref.build_batch: OK pages of every
+    bucket, flips, blank and near-blank pages) on the device with its
+    reference, built once for all variants."""
+    out = {}
+    for P, n in SCRUB_SHAPES:
+        pg, rows = scrub_ref.build_batch(P, n)
+        want = scrub_ref.classify(pg, P)
+        assert want[2]["n_ok"] and want[2]["n_blank"] and all(want[2]["ok_by_type"])
+        assert all(want[0][r] == scrub_ref.CORRUPT for r in rows["near_blank"].values())
+        out[(P, n)] = (scrub_gpu.to_dev(pg), want)
+    return out
+
+
+@pytest.mark.parametrize("tuned", ["default", "no_nt", "no_split", "rt_one_block", "grid_stride"], indirect=True)
+@pytest.mark.parametrize("P,n", SCRUB_SHAPES)
+def test_variant_scrub(tuned, scrub_batches, P, n):
+    """The fourth mode: classes, type bytes, summary and corrupt list are the
+    reference's under every variant, and OK exactly where validate says ok."""
+    d, want = scrub_batches[(P, n)]
+    cls = scrub_gpu.scrub_checked(d, P, n, want, reps=1)
+    ok, _ = pcs.pages_validate(d, P, n)
+    assert np.array_equal(cls.cpu().numpy() == pcs.PAGE_OK, ok.cpu().numpy() == 1), tuned
 
 
 @pytest.mark.parametrize("tuned", ["default", "no_nt", "rt_one_block", "x64_depth1", "x64_depth4", "x64_one_wave",

@@ -74,6 +74,59 @@ def test_built_batches_hold_every_case(P, n):
     assert (cls[rows["flipped"]] == scrub_ref.CORRUPT).all()
 
 
+def _has_all(offs, lo, hi):
+    return np.isin(np.arange(max(lo, 0), hi), offs).all()
+
+
+@pytest.mark.parametrize("P", [249, 1000, 4096, 5120, 8192, 65535, 65536, 131328, 135176])
+def test_walk_offsets_cover_what_they_claim(P):
+    offs = scrub_ref.walk_offsets(P)
+    assert offs.ndim == 1 and (np.diff(offs) > 0).all() and offs[0] >= 0 and offs[-1] < P
+    if P <= 5120:
+        assert np.array_equal(offs, np.arange(P))
+        return
+    assert _has_all(offs, 0, 1100) and _has_all(offs, P - 1100, P)
+    if P <= 65536:
+        k = offs // 16
+        assert np.array_equal(np.unique(k), np.arange((P + 15) // 16))  # every piece is hit
+        pairs = lambda a: {(int(x), int(y)) for x, y in zip(a, offs % 16)}
+        assert len(pairs(k % 16)) == 256            # (lane, byte-in-piece)
+        assert len(pairs((k // 16) % 4)) == 64      # (chunk, byte-in-piece)
+        for m in range(0, P + 1, 4096):
+            assert _has_all(offs, m - 24, min(m + 25, P)), m
+    else:
+        assert np.array_equal(np.unique(offs // 64), np.arange((P + 63) // 64))  # every stripe is hit
+
+
+@pytest.mark.parametrize("P", [249, 1000, 4096, 8192])
+def test_walk_batches_hold_every_case(P):
+    pg, rows = scrub_ref.build_walk_batch(P, seed=1)
+    n = len(pg)
+    offs, wrows = rows["offsets"], rows["walk_rows"]
+    assert np.array_equal(offs, scrub_ref.walk_offsets(P)) and len(set(wrows.tolist())) == len(offs)
+    assert rows["walk"] == dict(zip(offs.tolist(), wrows.tolist()))
+    control = sorted(r for kind in scrub_ref.CONTROL_KINDS for r in rows[kind])
+    assert control[:-1] == list(range(0, n - 1, 17)) and control[-1] == n - 1
+    assert sorted(control + wrows.tolist()) == list(range(n))
+    assert {0, n - 1} <= set(rows["blank"])
+    assert {r % 16 for r in control} == set(range(16))
+    # a walk page is zero but for one byte with one bit; all 8 bits at every byte-in-piece position
+    vals = pg[wrows, offs]
+    assert (pg[wrows].astype(bool).sum(axis=1) == 1).all() and np.isin(vals, 1 << np.arange(8)).all()
+    assert {(int(p), int(v)) for p, v in zip(offs % 16, vals)} == {(p, 1 << b) for p in range(16) for b in range(8)}
+    hb = pg[rows["header_bit"]]
+    assert not hb[:, 8:].any()
+    assert [int(x) for x in np.ascontiguousarray(hb[:, :8]).view("<u8").ravel()] == \
+        [1 << ((r // 17) % 64) for r in rows["header_bit"]]
+    cls, types, s, bad = scrub_ref.classify(pg, P)
+    assert (cls[wrows] == scrub_ref.CORRUPT).all()
+    assert (cls[rows["header_bit"]] == scrub_ref.CORRUPT).all() and len(rows["header_bit"]) >= 1
+    assert (cls[rows["blank"]] == scrub_ref.BLANK).all() and s["n_blank"] == len(rows["blank"])
+    assert (cls[rows["zero_body_ok"]] == scrub_ref.OK).all() and (cls[rows["random_ok"]] == scrub_ref.OK).all()
+    assert s["n_ok"] == len(rows["zero_body_ok"]) + len(rows["random_ok"]) >= 2
+    assert set(types[rows["random_ok"]].tolist()) <= set(scrub_ref.TYPE_BYTES)
+
+
 def test_new_symbols_and_abi_7():
     so = pcs.lib()
     assert hasattr(so, "pcs_pages_scrub_dev") and hasattr(so, "pcs_pages_scrub_host")
