@@ -357,14 +357,23 @@ def test_host_batch_api(P):
 
 def test_host_batch_multi_chunk():
     # more than one 32 MiB staging slot: exercises the double-buffered pipeline
+    # every page has its own content, so a page gathered into the wrong place
+    # or a header scattered back to the wrong page shows in the headers
     P = 65536
     n = 1200
-    pages = [bytearray(P) for _ in range(n)]
+    raw = oracle.fill_pages(P, n, 0x5EED00C7).reshape(n, P)
+    pages = [bytearray(raw[i].tobytes()) for i in range(n)]
     for i in range(0, n, 37):
         pages[i][100:108] = i.to_bytes(8, "little")
+        raw[i, 100:108] = np.frombuffer(i.to_bytes(8, "little"), dtype=np.uint8)
+    want = oracle.pages_digest(raw, P)
+    assert np.unique(want).size == n
     pcs.set_checksums(pages, P)
+    got = np.array([int.from_bytes(p[:8], "little") for p in pages], dtype=np.uint64)
+    assert np.array_equal(got, want), np.flatnonzero(got != want)[:8]
+    assert all(bytes(p[8:]) == raw[i, 8:].tobytes() for i, p in enumerate(pages))  # bodies untouched
     ok, fb = pcs.validate_checksums(pages, P)
-    assert all(ok)
+    assert all(ok) and fb is None
     pages[1199][9] = 1
     ok, fb = pcs.validate_checksums(pages, P)
     assert fb == 1199 and sum(ok) == n - 1
