@@ -51,6 +51,8 @@ _SIGS = {
     "pcs_pages_scrub_host": [_vp, _u64, _u64, _vp, _vp, _vp, _vp, _u64],
     "pcs_scrub_extents_dev": [_vp, _u64, _vp, _vp, _u64, _vp],
     "pcs_pages_scrub_extents_host": [_vp, _u64, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64],
+    "pcs_scrub_files_dev": [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _u64, _vp],
+    "pcs_pages_scrub_files_host": [_vp, _u64, _u64, _vp, _u64, _vp, _vp, _vp, _u64],
     "pcs_desc_digest_dev": [_vp, _vp, _vp, _u64, _i32, _vp, _vp],
     "pcs_desc_validate_dev": [_vp, _vp, _vp, _u64, _i32, _vp, _vp, _vp],
     "pcs_desc_stamp_dev": [_vp, _vp, _vp, _u64, _i32, _vp],
@@ -337,6 +339,73 @@ def scrub_extents(cls, n: int | None = None, run_cap: int = 1024, stream=None):
     return d, words.view(EXTENT_DTYPE).reshape(-1)
 
 
+_FILE_REPORT_WORDS = 16  # pcs_file_report
+_FILES_SUMMARY_WORDS = 12  # pcs_files_summary
+_FILES_SUMMARY_FIELDS = ("n_files", "n_pages", "n_ok", "n_corrupt", "n_blank", "n_corrupt_files", "n_hole_files",
+                         "n_bad_files", "n_unwritten_files", "first_bad_file", "n_listed", "invalid_file")
+# pcs_file_report: 128 bytes, 16 u64 words on the device and on the host
+FILE_REPORT_DTYPE = np.dtype([("first_page", "<u8"), ("n_pages", "<u8"), ("n_ok", "<u8"), ("n_corrupt", "<u8"),
+                              ("n_blank", "<u8"), ("ok_by_type", "<u8", (6,)), ("first_corrupt", "<u8"),
+                              ("written_pages", "<u8"), ("n_holes", "<u8"), ("n_hole_pages", "<u8"),
+                              ("first_hole", "<u8")])
+
+
+def file_report_dict(rec) -> dict:
+    """One pcs_file_report (a FILE_REPORT_DTYPE record or 16 u64 words) as a dict."""
+    if getattr(rec, "dtype", None) != FILE_REPORT_DTYPE:
+        rec = np.array([int(x) & NO_PAGE for x in rec], dtype=np.uint64).view(FILE_REPORT_DTYPE)[0]
+    return {k: rec[k].tolist() if k == "ok_by_type" else int(rec[k]) for k in FILE_REPORT_DTYPE.names}
+
+
+def files_summary_dict(words) -> dict:
+    """pcs_files_summary (12 u64 words) as a dict."""
+    return {k: int(x) & NO_PAGE for k, x in zip(_FILES_SUMMARY_FIELDS, words)}
+
+
+def scrub_files_async(cls, types, file_first, n: int | None = None, n_files: int | None = None, reports=None,
+                      summary=None, bad=None, bad_cap: int = 1024, stream=None):
+    """pcs_scrub_files_dev, enqueue only: cls and types are device uint8
+    tensors of a scrub's class and type bytes, file_first a device int64
+    tensor of n_files + 1 page boundaries; returns the device tensors (reports
+    as n_files x 16 int64 words, summary words, bad file indices), valid once
+    the stream is synchronised.  bad_cap 0 passes a NULL list."""
+    if n is None:
+        n = cls.numel()
+    if n_files is None:
+        n_files = file_first.numel() - 1
+    if reports is None:
+        reports = torch.empty((max(n_files, 1), _FILE_REPORT_WORDS), dtype=torch.int64, device=cls.device)
+    if summary is None:
+        summary = torch.empty(_FILES_SUMMARY_WORDS, dtype=torch.int64, device=cls.device)
+    if bad is None and bad_cap:
+        bad = torch.empty(bad_cap, dtype=torch.int64, device=cls.device)
+    _call("pcs_scrub_files_dev", _ptr(cls), _ptr(types), n, _ptr(file_first), n_files, _ptr(reports), _ptr(summary),
+          _ptr(bad) if bad_cap else 0, bad_cap, _stream(stream))
+    return reports, summary, bad
+
+
+def scrub_files(cls, types, file_first, bad_cap: int = 1024, stream=None):
+    """One report per data file of a scrubbed batch: -> (structured array
+    (FILE_REPORT_DTYPE) of n_files reports, summary dict, array of the
+    n_listed smallest bad file indices).  file_first may be a device tensor or
+    any host sequence of n_files + 1 ascending page boundaries.  Waits for the
+    stream.  With invalid boundaries (summary["invalid_file"] set) the reports
+    are not written and come back empty."""
+    if not isinstance(file_first, torch.Tensor):
+        host = np.ascontiguousarray(file_first, dtype=np.uint64).view(np.int64)
+        file_first = torch.from_numpy(host).to(cls.device)
+    n_files = file_first.numel() - 1
+    reports, summary, bad = scrub_files_async(cls, types, file_first, None, n_files, None, None, None, bad_cap, stream)
+    if stream is not None:  # the copies below are ordered on torch's current stream only
+        _call("pcs_synchronize", _stream(stream))
+    d = files_summary_dict(summary.cpu().tolist())
+    if d["invalid_file"] != NO_PAGE:
+        return np.zeros(0, dtype=FILE_REPORT_DTYPE), d, np.zeros(0, dtype=np.uint64)
+    recs = np.ascontiguousarray(reports[:n_files].cpu().numpy()).view(np.uint64).view(FILE_REPORT_DTYPE).reshape(-1)
+    listed = bad[: d["n_listed"]].cpu().numpy().view(np.uint64) if bad is not None else np.zeros(0, dtype=np.uint64)
+    return recs, d, listed
+
+
 def desc_digest(base, off, length, n: int, algo: int = XXH3_64, out=None, stream=None):
     if out is None:
         out = torch.empty(n, dtype=torch.int64, device=base.device)
@@ -601,6 +670,29 @@ def scrub_extents_host(pages: list, page_size: int, run_cap: int = 1024, corrupt
     arr, _keep = _page_ptrs(pages)
     ptrs = np.array([arr[i] or 0 for i in range(len(pages))], dtype=np.uint64)
     return scrub_extents_ptrs(ptrs, page_size, run_cap, corrupt_cap, per_page)
+
+
+def scrub_files_ptrs(ptrs, page_size: int, file_first, bad_cap: int = 1024):
+    """pcs_pages_scrub_files_host over raw host page addresses and n_files + 1
+    page boundaries that cover them -> (structured array (FILE_REPORT_DTYPE) of
+    n_files reports, summary dict, array of the n_listed smallest bad files)."""
+    ptrs = np.ascontiguousarray(ptrs, dtype=np.uint64)
+    first = np.ascontiguousarray(file_first, dtype=np.uint64)
+    n_files = len(first) - 1
+    reports = np.zeros(max(1, n_files), dtype=FILE_REPORT_DTYPE)
+    summary = np.zeros(_FILES_SUMMARY_WORDS, dtype=np.uint64)
+    bad = np.zeros(max(1, bad_cap), dtype=np.uint64)
+    _call("pcs_pages_scrub_files_host", ptrs.ctypes.data, page_size, len(ptrs), first.ctypes.data, n_files,
+          reports.ctypes.data, summary.ctypes.data, bad.ctypes.data if bad_cap else 0, bad_cap)
+    d = files_summary_dict(summary)
+    return reports[:n_files], d, bad[: d["n_listed"]]
+
+
+def scrub_files_host(pages: list, page_size: int, file_first, bad_cap: int = 1024):
+    """Scrub scattered host buffers (bytearrays) cut into files: see scrub_files_ptrs."""
+    arr, _keep = _page_ptrs(pages)
+    ptrs = np.array([arr[i] or 0 for i in range(len(pages))], dtype=np.uint64)
+    return scrub_files_ptrs(ptrs, page_size, file_first, bad_cap)
 
 
 class ValidateService:

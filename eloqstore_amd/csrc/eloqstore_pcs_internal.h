@@ -30,6 +30,15 @@ hipError_t run_scrub(const uint8_t* pages, uint64_t page_size, uint64_t n, uint8
 hipError_t run_extents(const uint8_t* cls, uint64_t n, uint64_t* summary, uint64_t* runs, uint64_t cap,
                        hipStream_t s);
 
+// Per-file reports of a scrub's class and type bytes cls / type[0 .. n): file f
+// is pages [first[f], first[f + 1]) (first: n_files + 1 device words, checked
+// on the device).  reports = 16 words per file (pcs_file_report), summary = the
+// 12 words of pcs_files_summary, list[0 .. min(n_bad_files, cap)) = the
+// smallest bad file indices, ascending.  All device memory; enqueues on s and
+// never waits.
+hipError_t run_files(const uint8_t* cls, const uint8_t* type, uint64_t n, const uint64_t* first, uint64_t n_files,
+                     uint64_t* reports, uint64_t* summary, uint64_t* list, uint64_t cap, hipStream_t s);
+
 // Descriptor batch: range i =[base + off[i], +len[i]).  skip = 8 applies the
 // page convention (digest over [8, len), stored digest at [0, 8)); skip = 0
 // hashes the raw range.  seed is used by XXH64 only (XXH3 path is seed 0).

@@ -120,6 +120,73 @@ ExtentReport ScrubExtents(std::span<const char* const> pages, size_t page_size, 
     return report;
 }
 
+int TryScrubFiles(std::span<const char* const> pages, size_t page_size, std::span<const uint64_t> file_first_page,
+                  FilesReport& report, size_t max_listed) {
+    static_assert(sizeof(FileReport) == sizeof(pcs_file_report), "FileReport mirrors pcs_file_report");
+    if (file_first_page.empty()) return pcs_pages_scrub_files_host(nullptr, page_size, 0, nullptr, 0, nullptr, nullptr, nullptr, 0);
+    const size_t n_files = file_first_page.size() - 1;
+    std::vector<pcs_file_report> reports(n_files);
+    report.bad_files.assign(std::min(max_listed, n_files), 0);
+    pcs_files_summary sum{};
+    const int rc = pcs_pages_scrub_files_host(reinterpret_cast<const void* const*>(pages.data()), page_size,
+                                              pages.size(), file_first_page.data(), n_files, reports.data(), &sum,
+                                              report.bad_files.data(), report.bad_files.size());
+    if (rc != PCS_OK) return rc;
+    report.files.resize(n_files);
+    for (size_t f = 0; f < n_files; ++f) {
+        const pcs_file_report& r = reports[f];
+        FileReport& o = report.files[f];
+        o.first_page = r.first_page;
+        o.n_pages = r.n_pages;
+        o.n_ok = r.n_ok;
+        o.n_corrupt = r.n_corrupt;
+        o.n_blank = r.n_blank;
+        for (int k = 0; k < 6; ++k) o.ok_by_type[k] = r.ok_by_type[k];
+        o.first_corrupt = r.first_corrupt;
+        o.written_pages = r.written_pages;
+        o.n_holes = r.n_holes;
+        o.n_hole_pages = r.n_hole_pages;
+        o.first_hole = r.first_hole;
+    }
+    report.n_pages = sum.n_pages;
+    report.n_ok = sum.n_ok;
+    report.n_corrupt = sum.n_corrupt;
+    report.n_blank = sum.n_blank;
+    report.n_corrupt_files = sum.n_corrupt_files;
+    report.n_hole_files = sum.n_hole_files;
+    report.n_bad_files = sum.n_bad_files;
+    report.n_unwritten_files = sum.n_unwritten_files;
+    report.first_bad_file = sum.first_bad_file;
+    report.bad_files.resize(sum.n_listed);
+    return PCS_OK;
+}
+
+FilesReport ScrubFiles(std::span<const char* const> pages, size_t page_size, std::span<const uint64_t> file_first_page,
+                       size_t max_listed) {
+    FilesReport report;
+    if (int rc = TryScrubFiles(pages, page_size, file_first_page, report, max_listed)) die("ScrubFiles", rc);
+    return report;
+}
+
+int TryScrubFiles(std::span<const char* const> pages, size_t page_size, uint64_t pages_per_file, FilesReport& report,
+                  size_t max_listed) {
+    std::vector<uint64_t> first;  // left empty for pages_per_file == 0: refused as a null boundary array
+    if (pages_per_file) {
+        const uint64_t n = pages.size(), n_files = n / pages_per_file + (n % pages_per_file ? 1 : 0);
+        first.resize(n_files + 1);
+        for (uint64_t f = 0; f < n_files; ++f) first[f] = f * pages_per_file;
+        first[n_files] = n;
+    }
+    return TryScrubFiles(pages, page_size, std::span<const uint64_t>(first), report, max_listed);
+}
+
+FilesReport ScrubFiles(std::span<const char* const> pages, size_t page_size, uint64_t pages_per_file,
+                       size_t max_listed) {
+    FilesReport report;
+    if (int rc = TryScrubFiles(pages, page_size, pages_per_file, report, max_listed)) die("ScrubFiles", rc);
+    return report;
+}
+
 void RegisterPagePool(void* base, size_t bytes) {
     if (int rc = pcs_host_register(base, bytes)) die("RegisterPagePool", rc);
 }

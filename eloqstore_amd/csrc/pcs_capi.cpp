@@ -8,6 +8,7 @@
 #include "eloqstore_pcs_internal.h"
 #include "region_registry.h"
 #include "extent_merge.h"
+#include "file_merge.h"
 #include "scrub_merge.h"
 
 #include <hip/hip_runtime.h>
@@ -291,6 +292,14 @@ struct Slot {
     pcs_extent* d_runs = nullptr;
     size_t cap_runs = 0;
     uint64_t runs_listed = 0;  // runs asked of the chunk in flight
+    // scrub files only (ensure_files_slot): the chunk-local boundaries, the parts' reports, the chunk's summary
+    uint64_t* h_bounds = nullptr;  // pinned
+    uint64_t* d_bounds = nullptr;
+    pcs_file_report* h_parts = nullptr;  // pinned
+    pcs_file_report* d_parts = nullptr;
+    pcs_files_summary* d_fsum = nullptr;
+    size_t cap_parts = 0;
+    uint64_t part_file = 0, parts = 0;  // first file and parts of the chunk in flight
 };
 
 constexpr int kSlots = 3;  // H2D of chunk k+1 || kernel k || D2H k-1
@@ -319,6 +328,11 @@ struct HostCtx {
             (void)hipFree(s.d_ext);
             (void)hipHostFree(s.h_runs);
             (void)hipFree(s.d_runs);
+            (void)hipHostFree(s.h_bounds);
+            (void)hipFree(s.d_bounds);
+            (void)hipHostFree(s.h_parts);
+            (void)hipFree(s.d_parts);
+            (void)hipFree(s.d_fsum);
             if (s.stream) (void)hipStreamDestroy(s.stream);
         }
     }
@@ -723,6 +737,123 @@ int host_scrub(const void* const* pages, uint64_t P, uint64_t n, uint8_t* cls, u
             s.busy = false;
         }
     }
+    return rc;
+}
+
+// Scrub files' extra per-slot buffers: parts + 1 boundaries, parts reports, one summary.
+int ensure_files_slot(Slot& s, size_t parts) {
+    if (!s.d_fsum && hipMalloc(reinterpret_cast<void**>(&s.d_fsum), sizeof(pcs_files_summary)) != hipSuccess)
+        return fail(PCS_ERR_NOMEM, "scrub staging allocation failed");
+    if (parts > s.cap_parts) {
+        (void)hipHostFree(s.h_bounds);
+        (void)hipFree(s.d_bounds);
+        (void)hipHostFree(s.h_parts);
+        (void)hipFree(s.d_parts);
+        s.h_bounds = nullptr; s.d_bounds = nullptr;
+        s.h_parts = nullptr; s.d_parts = nullptr;
+        s.cap_parts = 0;
+        if (hipHostMalloc(reinterpret_cast<void**>(&s.h_bounds), (parts + 1) * 8, hipHostMallocDefault) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void**>(&s.d_bounds), (parts + 1) * 8) != hipSuccess ||
+            hipHostMalloc(reinterpret_cast<void**>(&s.h_parts), parts * sizeof(pcs_file_report), hipHostMallocDefault) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void**>(&s.d_parts), parts * sizeof(pcs_file_report)) != hipSuccess)
+            return fail(PCS_ERR_NOMEM, "scrub staging allocation failed");
+        s.cap_parts = parts;
+    }
+    return PCS_OK;
+}
+
+// pcs_pages_scrub_files_host: host_scrub's pipeline with, behind each chunk's
+// scrub, the file reduction over the chunk's class and type bytes while they
+// are on the device.  A chunk is cut at the boundaries of the non-empty files
+// that intersect it, clipped to the chunk (the files cover the batch, so these
+// cover the chunk); only the parts' reports come back and FileMerge folds each
+// into its file's report, in page order.  Empty files never reach the device.
+int host_scrub_files(const void* const* pages, uint64_t P, uint64_t n, const uint64_t* file_first, uint64_t n_files,
+                     pcs_file_report* reports, pcs_files_summary* summary, uint64_t* bad, uint64_t bad_cap) {
+    if (int rc = require_device()) return rc;
+    if (!scrub_page_size_ok(P)) return fail(PCS_ERR_INVALID, kScrubPageSize);
+    if (int rc = check_host_batch_args(pages, P, n, PCS_XXH3_64)) return rc;
+    std::vector<uint64_t> nonempty;  // the files that hold pages, ascending
+    for (uint64_t f = 0; f < n_files; ++f) {
+        reports[f] = pcs::FileMerge::empty(file_first[f]);
+        if (file_first[f + 1] > file_first[f]) nonempty.push_back(f);
+    }
+    int rc = PCS_OK;
+    if (n) {
+        int dev = 0;
+        hipError_t e = hipGetDevice(&dev);
+        if (e != hipSuccess) return hip_fail(e, "hipGetDevice");
+        HostCtx& ctx = t_ctx[dev];
+        const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(n, kStageBytes / P));
+        const uint64_t max_parts = std::min<uint64_t>(chunk, nonempty.size());
+        const uint8_t* base = static_cast<const uint8_t*>(pages[0]);
+        const bool direct = contiguous_pinned(pages, n, P);
+        for (auto& s : ctx.slot) {
+            if ((rc = ensure_slot(s, direct ? 0 : chunk * P, chunk))) return rc;
+            if ((rc = ensure_scrub_slot(s, chunk, 0))) return rc;
+            if ((rc = ensure_files_slot(s, max_parts))) return rc;
+            if (direct && chunk * P > s.cap_dev_bytes) {  // device page buffers are still needed per slot
+                (void)hipFree(s.d_pages);
+                s.d_pages = nullptr;
+                s.cap_dev_bytes = 0;
+                if (hipMalloc(reinterpret_cast<void**>(&s.d_pages), chunk * P) != hipSuccess)
+                    return fail(PCS_ERR_NOMEM, "staging allocation failed");
+                s.cap_dev_bytes = chunk * P;
+            }
+        }
+        auto drain = [&](Slot& s) -> int {
+            if (!s.busy) return PCS_OK;
+            const hipError_t err = hipStreamSynchronize(s.stream);
+            s.busy = false;
+            if (err != hipSuccess) return hip_fail(err, "hipStreamSynchronize");
+            for (uint64_t j = 0; j < s.parts; ++j) pcs::FileMerge::add(reports[nonempty[s.part_file + j]], s.h_parts[j]);
+            return PCS_OK;
+        };
+        uint64_t k = 0, at = 0;  // at: the first non-empty file that reaches into the chunk
+        for (uint64_t first = 0; first < n && rc == PCS_OK; first += chunk, ++k) {
+            Slot& s = ctx.slot[k % kSlots];
+            if ((rc = drain(s))) break;  // chunk k - kSlots: slots drain in page order
+            const uint64_t cnt = std::min(chunk, n - first), stop = first + cnt;
+            if (!direct) gather(s.h_pages, pages, first, cnt, P);
+            count(direct ? PCS_COUNTER_DIRECT_DMA_CHUNKS : PCS_COUNTER_GATHER_CHUNKS);
+            s.first = first;
+            s.count = cnt;
+            s.part_file = at;
+            s.parts = 0;
+            for (uint64_t i = at; i < nonempty.size() && file_first[nonempty[i]] < stop; ++i) {
+                s.h_bounds[s.parts++] = std::max(file_first[nonempty[i]], first) - first;
+                if (file_first[nonempty[i] + 1] <= stop) at = i + 1;  // the file ends in this chunk
+            }
+            s.h_bounds[s.parts] = cnt;
+            e = hipMemcpyAsync(s.d_pages, direct ? base + first * P : s.h_pages, cnt * P, hipMemcpyHostToDevice, s.stream);
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(s.d_bounds, s.h_bounds, (s.parts + 1) * 8, hipMemcpyHostToDevice, s.stream);
+            if (e == hipSuccess)
+                e = pcs::run_scrub(s.d_pages, P, cnt, s.d_ok, s.d_type, reinterpret_cast<uint64_t*>(s.d_sum), nullptr, 0,
+                                   s.stream);
+            if (e == hipSuccess)
+                e = pcs::run_files(s.d_ok, s.d_type, cnt, s.d_bounds, s.parts, reinterpret_cast<uint64_t*>(s.d_parts),
+                                   reinterpret_cast<uint64_t*>(s.d_fsum), nullptr, 0, s.stream);
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(s.h_parts, s.d_parts, s.parts * sizeof(pcs_file_report), hipMemcpyDeviceToHost, s.stream);
+            if (e != hipSuccess) {
+                rc = hip_fail(e, "host scrub enqueue");
+                break;
+            }
+            s.busy = true;
+        }
+        // oldest chunk first: slot k % kSlots holds chunk k - kSlots
+        for (int j = 0; j < kSlots; ++j) {
+            Slot& s = ctx.slot[(k + j) % kSlots];
+            if (rc == PCS_OK) {
+                rc = drain(s);
+            } else if (s.busy) {  // failed: let the slot's work finish, merge nothing more
+                (void)hipStreamSynchronize(s.stream);
+                s.busy = false;
+            }
+        }
+    }
+    if (rc == PCS_OK) pcs::files_summarize(reports, n_files, summary, bad, bad_cap);
     return rc;
 }
 
@@ -1637,6 +1768,40 @@ int pcs_pages_scrub_extents_host(const void* const* pages, uint64_t page_size, u
     if (run_cap && !runs) return fail(PCS_ERR_INVALID, "runs is null with run_cap > 0");
     if (injected_failure()) return fail(PCS_ERR_HIP, "injected failure (PCS_TUNE_FAIL_INJECT)");
     return host_scrub(pages, page_size, n_pages, cls, type, summary, corrupt, corrupt_cap, ext, runs, run_cap);
+}
+
+int pcs_scrub_files_dev(const uint8_t* d_class, const uint8_t* d_type, uint64_t n_pages, const uint64_t* d_file_first,
+                        uint64_t n_files, pcs_file_report* d_reports, pcs_files_summary* d_summary, uint64_t* d_bad,
+                        uint64_t bad_cap, pcs_stream_t stream) {
+    static_assert(sizeof(pcs_file_report) == 16 * sizeof(uint64_t), "pcs_file_report is 16 x u64");
+    static_assert(sizeof(pcs_files_summary) == 12 * sizeof(uint64_t), "pcs_files_summary is 12 x u64");
+    if (int rc = require_device()) return rc;
+    if (n_pages && !d_class) return fail(PCS_ERR_INVALID, "d_class is null");
+    if (n_pages && !d_type) return fail(PCS_ERR_INVALID, "d_type is null");
+    if (n_files && !d_file_first) return fail(PCS_ERR_INVALID, "d_file_first is null");
+    if (n_files && !d_reports) return fail(PCS_ERR_INVALID, "d_reports is null");
+    if (!d_summary) return fail(PCS_ERR_INVALID, "d_summary is null");
+    if (bad_cap && !d_bad) return fail(PCS_ERR_INVALID, "d_bad is null with bad_cap > 0");
+    return finish(pcs::run_files(d_class, d_type, n_pages, d_file_first, n_files, reinterpret_cast<uint64_t*>(d_reports),
+                                 reinterpret_cast<uint64_t*>(d_summary), d_bad, bad_cap,
+                                 reinterpret_cast<hipStream_t>(stream)),
+                  "scrub files kernel launch");
+}
+
+int pcs_pages_scrub_files_host(const void* const* pages, uint64_t page_size, uint64_t n_pages,
+                               const uint64_t* file_first, uint64_t n_files, pcs_file_report* reports,
+                               pcs_files_summary* summary, uint64_t* bad, uint64_t bad_cap) {
+    if (!file_first) return fail(PCS_ERR_INVALID, "file_first is null");
+    if (n_files && !reports) return fail(PCS_ERR_INVALID, "reports is null");
+    if (!summary) return fail(PCS_ERR_INVALID, "summary is null");
+    if (bad_cap && !bad) return fail(PCS_ERR_INVALID, "bad is null with bad_cap > 0");
+    if (file_first[0] != 0) return fail(PCS_ERR_INVALID, "file_first[0] is not 0: the files must cover the batch");
+    for (uint64_t f = 0; f < n_files; ++f)
+        if (file_first[f] > file_first[f + 1]) return fail(PCS_ERR_INVALID, "file_first decreases");
+    if (file_first[n_files] != n_pages)
+        return fail(PCS_ERR_INVALID, "file_first[n_files] is not n_pages: the files must cover the batch");
+    if (injected_failure()) return fail(PCS_ERR_HIP, "injected failure (PCS_TUNE_FAIL_INJECT)");
+    return host_scrub_files(pages, page_size, n_pages, file_first, n_files, reports, summary, bad, bad_cap);
 }
 
 int pcs_pages_stamp_dev(void* d_pages, uint64_t page_size, uint64_t n_pages, int algo, pcs_stream_t stream) {

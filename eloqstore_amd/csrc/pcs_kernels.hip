@@ -2192,6 +2192,326 @@ hipError_t run_extents(const uint8_t* cls, uint64_t n, uint64_t* summary, uint64
     return e;
 }
 
+// ---------------------------------------------------------------------------
+// Scrub files (pcs_scrub_files_dev): one report per data file of a batch from
+// the class and type bytes a scrub wrote.  File f is pages [first[f],
+// first[f + 1]); the boundaries live on the device, so nothing here may trust
+// them.  A segmented form of the two reductions above, four launches ordered
+// by construction (no atomic on global memory):
+//   k_files_plan     one block, rounds of 256 x kFilesPerThread files, each
+//                    thread taking consecutive files so that a round's loads
+//                    are in flight together: checks every boundary pair (first[f] <=
+//                    first[f + 1] <= n) and scans the files' work items, an
+//                    item being a span of at most kScrubSpan pages that never
+//                    crosses a file boundary: items_before[f] = sum of
+//                    ceil(len / kScrubSpan) over the files before f.  The
+//                    first invalid file and the item total go into two status
+//                    words; every later kernel leaves at once when the status
+//                    names an invalid file, so no page index is ever formed
+//                    from an unchecked boundary;
+//   k_files_count    one block per item (the host sizes the grid by the bound
+//                    n / kScrubSpan + n_files; blocks past the total leave):
+//                    finds its file by a block-uniform binary search over
+//                    items_before, reads its span's class and type bytes,
+//                    clipped to the file, and writes a record: the eight
+//                    scrub counters, the first corrupt page, the blank-run
+//                    starts, the first of them and the last non-blank page.
+//                    The byte before a lane's pages is read only inside the
+//                    file: a file's first page has no predecessor;
+//   k_files_reduce   a wave per file over the file's contiguous records: the
+//                    16-word report (hole fields derived as k_extent_scan
+//                    derives them) and a flag byte (corrupt, hole, unwritten);
+//   k_files_summary  one block, the same rounds: totals, an exclusive scan of
+//                    the bad flags and the capped ascending list of bad files.
+// ---------------------------------------------------------------------------
+constexpr int kFileRec = 12;  // u32 per record: corrupt, blank, ok_by_type[6], first corrupt, blank-run starts, first blank-run start, last non-blank + 1
+constexpr int kFileReportWords = 16;    // pcs_file_report
+constexpr int kFilesSummaryWords = 12;  // pcs_files_summary
+constexpr uint32_t kFileCorrupt = 1, kFileHole = 2, kFileUnwritten = 4;  // flag byte of a file
+constexpr int kFilesPerThread = 8;  // consecutive files per thread and round of the two one-block kernels
+
+__device__ __forceinline__ uint64_t wave_min(uint64_t v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        const uint64_t t = __shfl_xor((unsigned long long)v, d, 64);
+        if (t < v) v = t;
+    }
+    return v;
+}
+__device__ __forceinline__ uint64_t wave_max(uint64_t v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        const uint64_t t = __shfl_xor((unsigned long long)v, d, 64);
+        if (t > v) v = t;
+    }
+    return v;
+}
+
+__global__ __launch_bounds__(256) void k_files_plan(const uint64_t* __restrict__ first, uint64_t n_files, uint64_t n,
+                                                   uint64_t* __restrict__ items_before,
+                                                   uint64_t* __restrict__ status) {
+    __shared__ uint64_t w4[4];
+    __shared__ unsigned long long bad;
+    if (threadIdx.x == 0) bad = ~0ull;
+    __syncthreads();
+    uint64_t items = 0;        // items of the files before this round (uniform)
+    uint64_t invalid = ~0ull;  // this thread's first invalid file
+    for (uint64_t base = 0; base < n_files; base += 256 * kFilesPerThread) {
+        const uint64_t f0 = base + (uint64_t)threadIdx.x * kFilesPerThread;  // this thread's consecutive files
+        uint64_t c[kFilesPerThread], sum = 0;
+        uint64_t a = f0 < n_files ? first[f0] : 0;
+#pragma unroll
+        for (int k = 0; k < kFilesPerThread; ++k) {
+            c[k] = 0;
+            if (f0 + k < n_files) {
+                const uint64_t b = first[f0 + k + 1];
+                if (a > b || b > n) {
+                    if (invalid == ~0ull) invalid = f0 + k;
+                } else {
+                    c[k] = (b - a + kScrubSpan - 1) / kScrubSpan;
+                }
+                a = b;
+            }
+            sum += c[k];
+        }
+        uint64_t total;
+        uint64_t run = items + block_excl_scan(sum, w4, total);
+#pragma unroll
+        for (int k = 0; k < kFilesPerThread; ++k) {
+            if (f0 + k < n_files) items_before[f0 + k] = run;
+            run += c[k];
+        }
+        items += total;
+        __syncthreads();
+    }
+    if (invalid != ~0ull) atomicMin(&bad, (unsigned long long)invalid);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        items_before[n_files] = items;
+        status[0] = bad;
+        status[1] = items;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_files_count(const uint8_t* __restrict__ cls, const uint8_t* __restrict__ type,
+                                                    const uint64_t* __restrict__ first, uint64_t n_files,
+                                                    const uint64_t* __restrict__ items_before,
+                                                    const uint64_t* __restrict__ status, uint32_t* __restrict__ rec) {
+    const uint64_t item = blockIdx.x;
+    if (status[0] != ~0ull || item >= status[1]) return;  // uniform over the block
+    // the file that holds the item: items_before[lo] <= item < items_before[hi] (empty files share their
+    // successor's count, so the search ends on the file that has items)
+    uint64_t lo = 0, hi = n_files;
+    while (hi - lo > 1) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (items_before[mid] <= item) lo = mid;
+        else hi = mid;
+    }
+    const uint64_t begin = first[lo], end = first[lo + 1];
+    const uint64_t s0 = begin + (item - items_before[lo]) * kScrubSpan;
+    const uint64_t s1 = end - s0 < kScrubSpan ? end : s0 + kScrubSpan;
+    __shared__ uint32_t cnt[kFileRec];
+    if (threadIdx.x < kFileRec) cnt[threadIdx.x] = (threadIdx.x == 8 || threadIdx.x == 10) ? kExtentNone : 0u;
+    __syncthreads();
+    const uint64_t p0 = s0 + threadIdx.x * 16u;
+    uint64_t pack = 0;  // eight 8-bit counters (at most 16 each): corrupt, blank, ok by type bucket 0..5
+    uint32_t first_corrupt = kExtentNone, first_blank = kExtentNone, last_written = 0, nstarts = 0;
+    if (p0 < s1) {
+        const uint64_t left = s1 - p0;
+        uint64_t cl, ch, tl, th;
+        ld_bytes16(cls + p0, left, 0xFF, cl, ch);
+        ld_bytes16(type + p0, left, 0, tl, th);
+        const uint32_t valid = left >= 16 ? 0xFFFFu : (1u << left) - 1u;
+        uint32_t blank = 0;
+#pragma unroll
+        for (int k = 15; k >= 0; --k) {
+            const uint32_t c = byte_of(cl, ch, k), t = byte_of(tl, th, k);
+            const int bucket = t < 4 ? (int)t : t == 255 ? 4 : 5;
+            const int field = c == kClassCorrupt ? 0 : c == kClassBlank ? 1 : 2 + bucket;
+            pack += (c <= kClassBlank) ? 1ull << (8 * field) : 0;
+            if (c == kClassCorrupt) first_corrupt = threadIdx.x * 16u + k;
+            blank |= (c == kClassBlank ? 1u : 0u) << k;
+        }
+        blank &= valid;
+        // a blank page starts a blank run unless the page before it, in the same file, is blank
+        const uint32_t prev_blank = (p0 > begin && cls[p0 - 1] == kClassBlank) ? 1u : 0u;
+        const uint32_t starts = blank & ~((blank << 1) | prev_blank);
+        nstarts = __builtin_popcount(starts);
+        if (starts) first_blank = threadIdx.x * 16u + __builtin_ctz(starts);
+        if (const uint32_t w = valid & ~blank) last_written = threadIdx.x * 16u + (32 - __builtin_clz(w));
+    }
+    auto widen = [](uint32_t v) {
+        return (uint64_t)(v & 0xFF) | (uint64_t)((v >> 8) & 0xFF) << 16 | (uint64_t)((v >> 16) & 0xFF) << 32 |
+               (uint64_t)(v >> 24) << 48;
+    };
+    const uint64_t a = wave_sum(widen((uint32_t)pack)), b = wave_sum(widen((uint32_t)(pack >> 32)));
+    const uint64_t st = wave_sum(nstarts);
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int f = 0; f < 4; ++f) {
+            if (const uint32_t x = (uint32_t)(a >> (16 * f)) & 0xFFFF) atomicAdd(&cnt[f], x);
+            if (const uint32_t x = (uint32_t)(b >> (16 * f)) & 0xFFFF) atomicAdd(&cnt[4 + f], x);
+        }
+        if (st) atomicAdd(&cnt[9], (uint32_t)st);
+    }
+    if (first_corrupt != kExtentNone) atomicMin(&cnt[8], first_corrupt);
+    if (first_blank != kExtentNone) atomicMin(&cnt[10], first_blank);
+    if (last_written) atomicMax(&cnt[11], last_written);
+    __syncthreads();
+    if (threadIdx.x < kFileRec) rec[item * kFileRec + threadIdx.x] = cnt[threadIdx.x];
+}
+
+__global__ __launch_bounds__(256) void k_files_reduce(const uint64_t* __restrict__ first, uint64_t n_files,
+                                                     const uint64_t* __restrict__ items_before,
+                                                     const uint64_t* __restrict__ status,
+                                                     const uint32_t* __restrict__ rec, uint64_t* __restrict__ reports,
+                                                     uint8_t* __restrict__ flags) {
+    if (status[0] != ~0ull) return;
+    const int lane = threadIdx.x & 63;
+    const uint64_t f = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (f >= n_files) return;  // uniform over the wave
+    const uint64_t begin = first[f], len = first[f + 1] - begin;
+    const uint64_t r0 = items_before[f], r1 = items_before[f + 1];
+    uint64_t acc[9] = {};  // corrupt, blank, ok by type, blank-run starts
+    uint64_t first_corrupt = ~0ull, first_blank = ~0ull, written = 0;
+    for (uint64_t r = r0 + lane; r < r1; r += 64) {  // a lane's records ascend
+        const uint32_t* q = rec + r * kFileRec;
+        const uint64_t off = (r - r0) * kScrubSpan;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc[k] += q[k];
+        acc[8] += q[9];
+        if (q[8] != kExtentNone && first_corrupt == ~0ull) first_corrupt = off + q[8];
+        if (q[10] != kExtentNone && first_blank == ~0ull) first_blank = off + q[10];
+        if (q[11]) written = off + q[11];
+    }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) acc[k] = wave_sum(acc[k]);
+    first_corrupt = wave_min(first_corrupt);
+    first_blank = wave_min(first_blank);
+    written = wave_max(written);
+    // every blank run but the tail (the one that starts at `written`) lies below `written`
+    const uint64_t holes = acc[8] - (written < len ? 1 : 0);
+    if (lane < kFileReportWords) {
+        uint64_t v;
+        switch (lane) {
+            case 0: v = begin; break;
+            case 1: v = len; break;
+            case 2: v = acc[2] + acc[3] + acc[4] + acc[5] + acc[6] + acc[7]; break;
+            case 3: v = acc[0]; break;
+            case 4: v = acc[1]; break;
+            case 11: v = first_corrupt; break;
+            case 12: v = written; break;
+            case 13: v = holes; break;
+            case 14: v = acc[1] - (len - written); break;
+            case 15: v = holes ? first_blank : ~0ull; break;
+            default: v = acc[lane - 3]; break;  // 5..10: ok by type
+        }
+        reports[f * kFileReportWords + lane] = v;
+    }
+    if (lane == 0)
+        flags[f] = (uint8_t)((acc[0] ? kFileCorrupt : 0u) | (holes ? kFileHole : 0u) | (written ? 0u : kFileUnwritten));
+}
+
+__global__ __launch_bounds__(256) void k_files_summary(uint64_t n_files, const uint64_t* __restrict__ status,
+                                                      const uint64_t* __restrict__ reports,
+                                                      const uint8_t* __restrict__ flags, uint64_t cap,
+                                                      uint64_t* __restrict__ list, uint64_t* __restrict__ summary) {
+    __shared__ uint64_t w4[4];
+    __shared__ unsigned long long tot[8];  // pages, ok, corrupt, blank, corrupt files, hole files, unwritten files, first bad file
+    const uint64_t invalid = status[0];
+    if (invalid != ~0ull) {  // uniform: only n_files and the invalid file are reported
+        if (threadIdx.x < kFilesSummaryWords) summary[threadIdx.x] = threadIdx.x == 0 ? n_files : threadIdx.x == 11 ? invalid : 0;
+        return;
+    }
+    if (threadIdx.x < 8) tot[threadIdx.x] = threadIdx.x == 7 ? ~0ull : 0ull;
+    __syncthreads();
+    uint64_t n_bad = 0;    // bad files before this round (uniform)
+    uint64_t acc[7] = {};  // this thread's files
+    uint64_t first_bad = ~0ull;
+    for (uint64_t base = 0; base < n_files; base += 256 * kFilesPerThread) {
+        const uint64_t f0 = base + (uint64_t)threadIdx.x * kFilesPerThread;  // this thread's consecutive files
+        uint32_t bad = 0;  // bit k: file f0 + k is bad
+#pragma unroll
+        for (int k = 0; k < kFilesPerThread; ++k) {
+            const uint64_t f = f0 + k;
+            if (f < n_files) {
+                const uint64_t* q = reports + f * kFileReportWords;
+                const uint32_t fl = flags[f];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[j] += q[1 + j];  // n_pages, n_ok, n_corrupt, n_blank
+                acc[4] += fl & kFileCorrupt ? 1 : 0;
+                acc[5] += fl & kFileHole ? 1 : 0;
+                acc[6] += fl & kFileUnwritten ? 1 : 0;
+                if (fl & (kFileCorrupt | kFileHole)) {
+                    bad |= 1u << k;
+                    if (first_bad == ~0ull) first_bad = f;
+                }
+            }
+        }
+        uint64_t total;
+        uint64_t pos = n_bad + block_excl_scan(__builtin_popcount(bad), w4, total);
+        while (bad && pos < cap) {
+            list[pos++] = f0 + __builtin_ctz(bad);
+            bad &= bad - 1;
+        }
+        n_bad += total;
+        __syncthreads();
+    }
+#pragma unroll
+    for (int k = 0; k < 7; ++k) {
+        const uint64_t v = wave_sum(acc[k]);
+        if ((threadIdx.x & 63) == 0 && v) atomicAdd(&tot[k], (unsigned long long)v);
+    }
+    if (first_bad != ~0ull) atomicMin(&tot[7], (unsigned long long)first_bad);
+    __syncthreads();
+    if (threadIdx.x < kFilesSummaryWords) {
+        uint64_t v;
+        switch (threadIdx.x) {
+            case 0: v = n_files; break;
+            case 7: v = n_bad; break;
+            case 8: v = tot[6]; break;
+            case 9: v = tot[7]; break;
+            case 10: v = n_bad < cap ? n_bad : cap; break;
+            case 11: v = ~0ull; break;
+            default: v = tot[threadIdx.x - 1]; break;  // 1..6: pages, ok, corrupt, blank, corrupt files, hole files
+        }
+        summary[threadIdx.x] = v;
+    }
+}
+
+// Per-file reports of the class and type bytes cls / type[0 .. n) cut at the
+// device-resident boundaries first[0 .. n_files].  Nothing here waits for the
+// stream; the whole summary is written whatever n and n_files are.
+hipError_t run_files(const uint8_t* cls, const uint8_t* type, uint64_t n, const uint64_t* first, uint64_t n_files,
+                     uint64_t* reports, uint64_t* summary, uint64_t* list, uint64_t cap, hipStream_t s) {
+    // the most items valid boundaries can give: sum of ceil(len / span) <= sum of len / span + n_files
+    const uint64_t max_items = n / kScrubSpan + n_files;
+    if (n_files > 0x7FFFFFFFull || max_items > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    ScratchLease scratch(s);  // status, items before each file, records, flags
+    const size_t before_bytes = ((n_files + 1) * 8 + 15) & ~size_t(15);
+    const size_t rec_bytes = (max_items * kFileRec * 4 + 15) & ~size_t(15);
+    hipError_t e = scratch.get(16 + before_bytes + rec_bytes + n_files);
+    if (e != hipSuccess) return e;
+    uint64_t* status = static_cast<uint64_t*>(scratch.p);
+    uint64_t* items_before = status + 2;
+    uint32_t* rec = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(items_before) + before_bytes);
+    uint8_t* flags = reinterpret_cast<uint8_t*>(rec) + rec_bytes;
+    hipLaunchKernelGGL(k_files_plan, dim3(1), dim3(256), 0, s, first, n_files, n, items_before, status);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (max_items) {
+        hipLaunchKernelGGL(k_files_count, dim3((unsigned)max_items), dim3(256), 0, s, cls, type, first, n_files,
+                           items_before, status, rec);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    if (n_files) {
+        hipLaunchKernelGGL(k_files_reduce, dim3((unsigned)((n_files + 3) / 4)), dim3(256), 0, s, first, n_files,
+                           items_before, status, rec, reports, flags);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_files_summary, dim3(1), dim3(256), 0, s, n_files, status, reports, flags, cap, list, summary);
+    return hipGetLastError();
+}
+
 hipError_t scratch_acquire(size_t bytes, void** out, int* id) { return g_scratch.acquire(bytes, out, id); }
 hipError_t scratch_release(int id, hipStream_t s) { return g_scratch.release(id, s); }
 

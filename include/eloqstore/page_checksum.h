@@ -154,6 +154,43 @@ int TryScrubExtents(std::span<const char* const> pages, size_t page_size, Extent
 ExtentReport ScrubExtents(std::span<const char* const> pages, size_t page_size, size_t max_runs = 1024,
                           size_t max_listed = 1024);
 
+// Scrub files (pcs_pages_scrub_files_host): a batch that holds several data
+// files, scrubbed in one call, one report per file.  File f is pages
+// [file_first_page[f], file_first_page[f + 1]) of `pages`; the n_files + 1
+// boundaries ascend (equal neighbours: an empty file) from 0 to pages.size().
+// A file's counts are ScrubReport's and its written extent and holes
+// ExtentReport's over the file's pages alone, with file-local page indices: a
+// blank run never crosses a file boundary.  A file is bad when it has a
+// corrupt page or a hole; bad_files lists the first max_listed of them.
+struct FileReport {
+    uint64_t first_page = 0, n_pages = 0;  // the file's range in the batch
+    uint64_t n_ok = 0, n_corrupt = 0, n_blank = 0;
+    uint64_t ok_by_type[6] = {};           // as ScrubReport
+    uint64_t first_corrupt = UINT64_MAX;   // file-local
+    uint64_t written_pages = 0;            // file-local: 1 + the last non-blank page
+    uint64_t n_holes = 0, n_hole_pages = 0;
+    uint64_t first_hole = UINT64_MAX;      // file-local
+};
+struct FilesReport {
+    std::vector<FileReport> files;
+    uint64_t n_pages = 0, n_ok = 0, n_corrupt = 0, n_blank = 0;  // pages, over all files
+    uint64_t n_corrupt_files = 0, n_hole_files = 0, n_bad_files = 0, n_unwritten_files = 0;
+    uint64_t first_bad_file = UINT64_MAX;
+    std::vector<uint64_t> bad_files;       // the first min(n_bad_files, max_listed) bad files, ascending
+};
+// PCS_OK or a negative pcs_status (message in LastChecksumError()); a failed
+// call leaves the report unspecified.
+int TryScrubFiles(std::span<const char* const> pages, size_t page_size, std::span<const uint64_t> file_first_page,
+                  FilesReport& report, size_t max_listed = 1024);
+FilesReport ScrubFiles(std::span<const char* const> pages, size_t page_size,
+                       std::span<const uint64_t> file_first_page, size_t max_listed = 1024);
+// The store's usual case: files of pages_per_file pages each (> 0), the last
+// one short when pages.size() is no multiple of it.
+int TryScrubFiles(std::span<const char* const> pages, size_t page_size, uint64_t pages_per_file, FilesReport& report,
+                  size_t max_listed = 1024);
+FilesReport ScrubFiles(std::span<const char* const> pages, size_t page_size, uint64_t pages_per_file,
+                       size_t max_listed = 1024);
+
 // Registers a page-pool chunk or io_uring buffer ring once (PagesPool::Extend,
 // src/storage/page.cpp:95-120): batches whose pages all lie in registered
 // memory are then hashed in place over PCIe in one launch, with no gather

@@ -100,7 +100,9 @@ enum pcs_flags {
  *      pcs_page_class and struct pcs_scrub_summary; additive, no prototype changed.
  *      Added later under the same number, additive again (detect them by
  *      symbol): pcs_scrub_extents_dev / pcs_pages_scrub_extents_host, struct
- *      pcs_extent and struct pcs_extent_summary */
+ *      pcs_extent and struct pcs_extent_summary; pcs_scrub_files_dev /
+ *      pcs_pages_scrub_files_host, struct pcs_file_report and struct
+ *      pcs_files_summary */
 #define PCS_ABI_VERSION 7
 int pcs_abi_version(void);
 const char *pcs_version(void);
@@ -240,6 +242,74 @@ int pcs_pages_scrub_extents_host(const void *const *pages, uint64_t page_size, u
                                  uint8_t *cls, uint8_t *type, pcs_scrub_summary *summary,
                                  uint64_t *corrupt, uint64_t corrupt_cap, pcs_extent_summary *ext,
                                  pcs_extent *runs, uint64_t run_cap);
+
+/* ---- scrub files: one report per data file of a batch ----------------------
+ * A store holds data files, not one run of pages (KvOptions::pages_per_file_shift,
+ * include/kv_options.h: 1 << 18 pages by default, "a smaller file size like
+ * 4MB" recommended in append mode), so one device batch holds many files and
+ * the operator's question is which of them are damaged.  File f is pages
+ * [file_first[f], file_first[f + 1]) of the batch; file_first holds
+ * n_files + 1 entries.  A file's report is what the two reductions above give
+ * over that sub-range alone: the counting fields are pcs_pages_scrub_dev's
+ * summary of the file's class and type bytes, with first_corrupt FILE-LOCAL;
+ * written_pages, n_holes, n_hole_pages and first_hole are
+ * pcs_scrub_extents_dev's over the same bytes, file-local too.  Class bytes
+ * above 2 behave as there: counted nowhere, never blank.  A run never crosses
+ * a file boundary: a blank page that ends file f is f's tail, not f + 1's
+ * hole, and the byte before a file's first page is never read as its
+ * predecessor.  Empty files (file_first[f] == file_first[f + 1]) are legal:
+ * n_pages = 0, zero counts, UINT64_MAX in the three "first" fields.  A file is
+ * bad when it has a corrupt page or a hole; d_bad[0 .. n_listed) receives the
+ * n_listed = min(n_bad_files, bad_cap) SMALLEST bad file indices in ascending
+ * order (the same from call to call, no atomic append); entries at n_listed
+ * and beyond and reports at n_files and beyond are not written.
+ *
+ * pcs_scrub_files_dev reads only d_class and d_type[0 .. n_pages) (both
+ * required, any byte alignment) and the boundaries, which are a DEVICE array:
+ * a scrub can be followed by the cut with no host round trip.  The files need
+ * not cover the batch; pages in no file are in no report.  It enqueues on
+ * `stream`, never synchronises, and writes the whole summary on every call,
+ * n_files == 0 included.  d_bad may be NULL iff bad_cap == 0.  The host cannot
+ * see the boundaries, so the kernels check them: invalid_file is the first f
+ * with file_first[f] > file_first[f + 1] or file_first[f + 1] > n_pages; when
+ * it is set, every other summary word but n_files is 0 and no report or list
+ * entry is written, whatever the boundaries hold.
+ *
+ * pcs_pages_scrub_files_host is pcs_pages_scrub_host's staged pipeline (same
+ * page-size rule, PCS_TUNE_FAIL_INJECT and errors; never zero-copy, never the
+ * service) with host pointers throughout.  file_first is checked on the host
+ * (PCS_ERR_INVALID) and must cover the batch: file_first[0] == 0 and
+ * file_first[n_files] == n_pages.  Each 32 MiB chunk is scrubbed and cut, on
+ * the device, at the boundaries of the files that intersect it; only those
+ * partial reports come back (no per-page array), and a file's parts are folded
+ * in page order so that the result equals one pass over the file.  The summary
+ * and the bad list are built on the host; invalid_file is UINT64_MAX. */
+typedef struct pcs_file_report {          /* 16 x u64, the same layout on device and host */
+    uint64_t first_page, n_pages;         /* the file's range in the batch */
+    uint64_t n_ok, n_corrupt, n_blank;
+    uint64_t ok_by_type[6];               /* as pcs_scrub_summary */
+    uint64_t first_corrupt;               /* FILE-LOCAL page index, UINT64_MAX when none */
+    uint64_t written_pages;               /* file-local: 1 + last non-blank page, 0 when none */
+    uint64_t n_holes, n_hole_pages;       /* blank runs / pages below written_pages */
+    uint64_t first_hole;                  /* file-local, UINT64_MAX when none */
+} pcs_file_report;
+typedef struct pcs_files_summary {        /* 12 x u64, the same layout on device and host */
+    uint64_t n_files, n_pages;            /* n_pages = sum of the files' lengths */
+    uint64_t n_ok, n_corrupt, n_blank;    /* pages, over all files */
+    uint64_t n_corrupt_files;             /* files with n_corrupt > 0 */
+    uint64_t n_hole_files;                /* files with n_holes > 0 */
+    uint64_t n_bad_files;                 /* corrupt or hole */
+    uint64_t n_unwritten_files;           /* written_pages == 0 (empty files included) */
+    uint64_t first_bad_file;              /* UINT64_MAX when none */
+    uint64_t n_listed;                    /* min(n_bad_files, bad_cap) */
+    uint64_t invalid_file;                /* UINT64_MAX when the boundaries are valid */
+} pcs_files_summary;
+int pcs_scrub_files_dev(const uint8_t *d_class, const uint8_t *d_type, uint64_t n_pages,
+                        const uint64_t *d_file_first, uint64_t n_files, pcs_file_report *d_reports,
+                        pcs_files_summary *d_summary, uint64_t *d_bad, uint64_t bad_cap, pcs_stream_t stream);
+int pcs_pages_scrub_files_host(const void *const *pages, uint64_t page_size, uint64_t n_pages,
+                               const uint64_t *file_first, uint64_t n_files, pcs_file_report *reports,
+                               pcs_files_summary *summary, uint64_t *bad, uint64_t bad_cap);
 
 /* ---- device-resident descriptor batches (mixed page sizes) ----------------
  * Page i occupies [d_base + d_off[i], d_base + d_off[i] + d_len[i]).  Pages

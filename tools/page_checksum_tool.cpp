@@ -28,6 +28,13 @@
 //       Exit 2 if any page is corrupted, else 3 if there is a hole, else 0.
 //       An append-mode data file is written in page order, so only there does
 //       a hole (exit 3) mean a lost or trimmed write.
+//   page_checksum_tool --scrub-files <page_size> <file>...   scrub many data
+//       files in one pass: the files are packed back to back into the pinned
+//       chunks, each chunk is one pcs_pages_scrub_files_host call, and every
+//       file gets a report of its own (counts, written extent, holes).  One
+//       line per file that has a corrupted page or a hole, then the totals.
+//       Exit 2 if any file has a corrupted page, else 3 if any has a hole,
+//       else 0.  A file with no whole page is skipped with a warning.
 //   --scan/--stamp print a summary line with the GiB/s of the call; exit codes
 //   as above (--scan: 2 if any page is corrupted).
 #include <fcntl.h>
@@ -48,6 +55,7 @@
 #include "eloqstore/page_checksum.h"
 #include "eloqstore_pcs.h"
 #include "extent_merge.h"
+#include "file_merge.h"
 #include "scrub_merge.h"
 
 namespace {
@@ -74,8 +82,9 @@ void usage(const char* prog) {
                  "       %s --extents <file_path> [page_size_bytes]\n"
                  "           exit 2: corrupted pages; exit 3: a blank page below the last written one\n"
                  "           (a lost write only for append-mode files, which are written in page order)\n"
+                 "       %s --scrub-files <page_size_bytes> <file>...\n"
                  "       %s --gen <file_path> <n_pages> [page_size_bytes] [seed]\n",
-                 prog, prog, prog, prog, prog);
+                 prog, prog, prog, prog, prog, prog);
 }
 
 constexpr uint64_t kDefaultPageSize = 4096;  // KvOptions{}.data_page_size
@@ -435,6 +444,152 @@ int scrub(const char* path, const char* size_s, bool extents = false) {
     return total.n_corrupt ? 2 : 0;
 }
 
+// --scrub-files: many data files in one pass.  The files that hold at least
+// one whole page form one batch, back to back in argument order; the batch
+// flows through the two pinned chunks as in scrub() (chunk k + 1 is read on a
+// helper thread while chunk k is scrubbed), so a chunk holds whole files and
+// parts of files, and a file larger than what is left of a chunk continues in
+// the next one.  Each chunk is one pcs_pages_scrub_files_host call over the
+// chunk-local boundaries of its parts; a file's parts are folded by FileMerge.
+int scrub_files(const char* size_s, int n_paths, char** paths) {
+    uint64_t P = 0;
+    if (!parse_u64(size_s, P) || P < 249 || P > 0xFFFFFFFFull) {
+        std::fprintf(stderr, "Invalid page size: %s (scrub needs 249 <= page size < 2^32)\n", size_s);
+        return 1;
+    }
+    struct DataFile {
+        const char* path;
+        uint64_t first;  // the file's first page in the batch
+    };
+    std::vector<DataFile> files;
+    std::vector<Fd> fds(n_paths);
+    std::vector<int> fd_of;
+    std::vector<uint64_t> first{0};  // batch boundaries of the files scrubbed
+    uint64_t skipped = 0;
+    for (int i = 0; i < n_paths; ++i) {
+        fds[i].fd = open(paths[i], O_RDONLY);
+        struct stat st;
+        if (fds[i].fd < 0 || fstat(fds[i].fd, &st) != 0) {
+            std::fprintf(stderr, "Failed to open %s: %s\n", paths[i], std::strerror(errno));
+            return 1;
+        }
+        const uint64_t n = (uint64_t)st.st_size / P;  // a trailing partial page is ignored
+        if (n == 0) {
+            std::fprintf(stderr, "File %s holds no whole page of %llu bytes: skipped\n", paths[i], (unsigned long long)P);
+            ++skipped;
+            continue;
+        }
+        files.push_back(DataFile{paths[i], first.back()});
+        fd_of.push_back(fds[i].fd);
+        first.push_back(first.back() + n);
+    }
+    const uint64_t n = first.back(), n_files = files.size();
+    std::vector<pcs_file_report> reports(n_files);
+    for (uint64_t f = 0; f < n_files; ++f) reports[f] = pcs::FileMerge::empty(0);
+    const uint64_t chunk = std::max<uint64_t>(1, (env_u64("PCS_SCAN_CHUNK_MIB", 64) << 20) / P);
+    double secs = 0;
+    if (n) {
+        void* buf[2] = {nullptr, nullptr};
+        int rc = 0;
+        for (int k = 0; k < 2 && !rc; ++k) rc = pcs_host_alloc_pinned(std::min(chunk, n) * P, &buf[k]);
+        if (rc) {
+            std::fprintf(stderr, "GPU setup failed (%d): %s\n", rc, pcs_last_error());
+            for (void* b : buf) pcs_host_free_pinned(b);
+            return 1;
+        }
+        std::vector<const void*> ptrs(std::min(chunk, n));
+        {
+            // warm the GPU path before the clock starts, as --scan does
+            std::memset(buf[0], 0, (size_t)P);
+            const void* one = buf[0];
+            uint8_t c = 0;
+            pcs_scrub_summary warm{};
+            (void)pcs_pages_scrub_host(&one, P, 1, &c, nullptr, &warm, nullptr, 0);
+        }
+        const auto t0 = std::chrono::steady_clock::now();
+        // the files that reach into batch pages [p0, p0 + cnt): [lo, hi)
+        auto span_of = [&](uint64_t p0, uint64_t cnt, uint64_t& lo, uint64_t& hi) {
+            lo = (uint64_t)(std::upper_bound(first.begin(), first.end(), p0) - first.begin()) - 1;
+            hi = (uint64_t)(std::lower_bound(first.begin(), first.end(), p0 + cnt) - first.begin());
+        };
+        uint64_t failed_at = 0;
+        auto read_chunk = [&](uint64_t p0, int s) {
+            const uint64_t cnt = std::min(chunk, n - p0);
+            uint64_t lo, hi;
+            span_of(p0, cnt, lo, hi);
+            for (uint64_t f = lo; f < hi; ++f) {
+                const uint64_t a = std::max(first[f], p0), b = std::min(first[f + 1], p0 + cnt);
+                if (!pread_parallel(fd_of[f], static_cast<char*>(buf[s]) + (a - p0) * P, (b - a) * P, (a - first[f]) * P)) {
+                    failed_at = f;
+                    return false;
+                }
+            }
+            return true;
+        };
+        std::vector<uint64_t> bounds;
+        std::vector<pcs_file_report> parts;
+        pcs_files_summary part_sum;
+        bool read_ok = read_chunk(0, 0);
+        uint64_t k = 0;
+        for (uint64_t p0 = 0; p0 < n && !rc; p0 += chunk, ++k) {
+            const int s = (int)(k & 1);
+            if (!read_ok) {
+                std::fprintf(stderr, "read failed in %s: %s\n", files[failed_at].path, std::strerror(errno));
+                rc = 1;
+                break;
+            }
+            const uint64_t cnt = std::min(chunk, n - p0);
+            bool next_ok = true;
+            std::thread reader;
+            if (p0 + chunk < n) reader = std::thread([&, p0, s] { next_ok = read_chunk(p0 + chunk, s ^ 1); });
+            const char* b = static_cast<const char*>(buf[s]);
+            for (uint64_t i = 0; i < cnt; ++i) ptrs[i] = b + i * P;
+            uint64_t lo, hi;
+            span_of(p0, cnt, lo, hi);
+            bounds.clear();
+            for (uint64_t f = lo; f < hi; ++f) bounds.push_back(std::max(first[f], p0) - p0);
+            bounds.push_back(cnt);
+            parts.resize(hi - lo);
+            if (pcs_pages_scrub_files_host(ptrs.data(), P, cnt, bounds.data(), hi - lo, parts.data(), &part_sum, nullptr, 0)) {
+                rc = 1;
+            } else {
+                for (uint64_t f = lo; f < hi; ++f) pcs::FileMerge::add(reports[f], parts[f - lo]);
+            }
+            if (reader.joinable()) reader.join();
+            read_ok = next_ok;
+        }
+        secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        for (void* b : buf) pcs_host_free_pinned(b);
+        if (rc) {
+            std::fprintf(stderr, "scrub failed: %s\n", pcs_last_error());
+            return 1;
+        }
+    }
+    pcs_files_summary total;
+    pcs::files_summarize(reports.data(), n_files, &total, nullptr, 0);
+    for (uint64_t f = 0; f < n_files; ++f) {
+        const pcs_file_report& r = reports[f];
+        if (!r.n_corrupt && !r.n_holes) continue;
+        std::printf("%s: %llu pages, written [0, %llu), %llu ok, %llu corrupted, %llu blank, %llu holes (%llu pages), ",
+                    files[f].path, (unsigned long long)r.n_pages, (unsigned long long)r.written_pages,
+                    (unsigned long long)r.n_ok, (unsigned long long)r.n_corrupt, (unsigned long long)r.n_blank,
+                    (unsigned long long)r.n_holes, (unsigned long long)r.n_hole_pages);
+        if (r.n_corrupt)
+            std::printf("first corrupted page at offset %llu\n", (unsigned long long)(r.first_corrupt * P));
+        else
+            std::printf("first hole at offset %llu\n", (unsigned long long)(r.first_hole * P));
+    }
+    const double gib = (double)(n * P) / (1024.0 * 1024.0 * 1024.0);
+    std::printf("Scrubbed %llu files, %llu pages of %llu bytes: %llu clean, %llu corrupted, %llu with holes, %llu unwritten",
+                (unsigned long long)n_files, (unsigned long long)n, (unsigned long long)P,
+                (unsigned long long)(n_files - total.n_bad_files - total.n_unwritten_files),
+                (unsigned long long)total.n_corrupt_files, (unsigned long long)total.n_hole_files,
+                (unsigned long long)total.n_unwritten_files);
+    if (skipped) std::printf(", %llu skipped", (unsigned long long)skipped);
+    std::printf(" (%.3f s, %.2f GiB/s incl. file I/O)\n", secs, secs > 0 ? gib / secs : 0.0);
+    return total.n_corrupt_files ? 2 : total.n_hole_files ? 3 : 0;
+}
+
 int gen(const char* path, const char* n_s, const char* size_s, const char* seed_s) {
     uint64_t n = 0, P = kDefaultPageSize, seed = 0x5EED0001;
     if (!parse_u64(n_s, n) || n == 0 || (size_s && (!parse_u64(size_s, P) || P < 8 || P % 8)) ||
@@ -481,6 +636,13 @@ int main(int argc, char** argv) {
             return 1;
         }
         return scrub(argv[2], argc == 4 ? argv[3] : nullptr, argv[1][2] == 'e');
+    }
+    if (argc >= 2 && !std::strcmp(argv[1], "--scrub-files")) {
+        if (argc < 4) {
+            usage(argv[0]);
+            return 1;
+        }
+        return scrub_files(argv[2], argc - 3, argv + 3);
     }
     if (argc >= 2 && !std::strcmp(argv[1], "--gen")) {
         if (argc < 4 || argc > 6) {
