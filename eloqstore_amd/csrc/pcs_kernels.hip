@@ -1796,7 +1796,18 @@ private:
             }
             const hipError_t q = hipEventQuery(b.done);
             if (q == hipErrorNotReady) continue;
-            if (q != hipSuccess) return q;
+            if (q != hipSuccess) {
+                // The query itself failed, so the buffer cannot be shown idle:
+                // leave it to a later call and take another.  Seen as
+                // hipErrorCapturedEvent with no capture anywhere in the process,
+                // for an event last recorded on a stream that no longer exists;
+                // the scratch of a caller whose stream is gone must not fail the
+                // next caller.  The error is cleared so that the launches that
+                // follow do not report it as theirs; a real device error comes
+                // back from them or from hipMalloc below.
+                (void)hipGetLastError();
+                continue;
+            }
             // An idle buffer above kKeepBytes serves only a request of at least
             // half its size; any other request gives it back, so one large
             // manifest or stamp does not pin its scratch for the process life.
