@@ -81,6 +81,8 @@ _SIGS = {
     "pcs_manifest_checksum_dev": [_vp, _u64, _vp, _vp],
     "pcs_manifest_checksum_host": [_vp, _u64, _P(_u64)],
     "pcs_manifest_validate_host": [_vp, _u64, _P(_i32)],
+    "pcs_manifest_scan_dev": [_vp, _u64, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _u64, _vp],
+    "pcs_manifest_scan_host": [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _u64],
     "pcs_set_tuning": [_i32, ctypes.c_int64],
     "pcs_get_tuning": [_i32],
     "pcs_counter": [_i32],
@@ -177,6 +179,7 @@ TUNE_SERVICE_SLOW_EXIT_TEST = 33  # test only
 TUNE_ZC_BATCH_EVENT = 34
 TUNE_SYNC_SPIN_US = 35
 TUNE_SERVICE_DEPARTURE = 36
+TUNE_MANIFEST_WALK_TILE = 38
 
 # PCS_PATH_* bits (pcs_last_path / pcs_batch_path)
 PATH_SERVED = 1
@@ -472,6 +475,86 @@ def manifest_validate_host(record: bytes) -> bool:
     v = ctypes.c_int(0)
     _call("pcs_manifest_validate_host", buf, len(record), ctypes.byref(v))
     return bool(v.value)
+
+
+# pcs_manifest_record (40 bytes), pcs_manifest_report and pcs_manifest_summary (12 u64 words each)
+MANIFEST_RECORD_DTYPE = np.dtype([("offset", "<u8"), ("stored", "<u8"), ("computed", "<u8"), ("payload_len", "<u4"),
+                                  ("root", "<u4"), ("ttl_root", "<u4"), ("ok", "<u4")])
+MANIFEST_REPORT_DTYPE = np.dtype([(k, "<u8") for k in (
+    "size", "n_records", "n_ok", "n_corrupt", "first_corrupt", "n_ok_after_corrupt", "valid_prefix_bytes",
+    "end_offset", "end_reason", "verdict", "first_record", "max_record_bytes")])
+MANIFEST_SUMMARY_DTYPE = np.dtype([("n_images", "<u8"), ("n_records", "<u8"), ("n_ok", "<u8"), ("n_corrupt", "<u8"),
+                                   ("n_by_verdict", "<u8", (5,)), ("first_bad_image", "<u8"), ("n_listed", "<u8"),
+                                   ("invalid_image", "<u8")])
+MANIFEST_END = ("clean", "short_header", "short_payload", "short_padding")
+MANIFEST_VERDICT = ("clean", "torn_tail", "broken", "bad_snapshot", "empty")
+
+
+def manifest_scan_async(base, img_off, img_size, align: int = 4096, total_bytes: int | None = None,
+                        n_images: int | None = None, reports=None, summary=None, records=None,
+                        record_cap: int = 1024, stream=None):
+    """pcs_manifest_scan_dev, enqueue only: base is a device uint8 tensor that
+    holds the images, img_off / img_size device int64 tensors of their offsets
+    and sizes; returns the device tensors (reports as n_images x 12 int64
+    words, the 12 summary words, records as record_cap x 40 bytes), valid once
+    the stream is synchronised.  record_cap 0 passes a NULL record array."""
+    if total_bytes is None:
+        total_bytes = base.numel()
+    if n_images is None:
+        n_images = img_off.numel()
+    if reports is None:
+        reports = torch.empty((max(n_images, 1), 12), dtype=torch.int64, device=base.device)
+    if summary is None:
+        summary = torch.empty(12, dtype=torch.int64, device=base.device)
+    if records is None and record_cap:
+        records = torch.empty((record_cap, 5), dtype=torch.int64, device=base.device)
+    _call("pcs_manifest_scan_dev", _ptr(base), total_bytes, _ptr(img_off), _ptr(img_size), n_images, align,
+          _ptr(reports), _ptr(summary), _ptr(records) if record_cap else 0, record_cap, _stream(stream))
+    return reports, summary, records
+
+
+def manifest_scan_dev(base, img_off, img_size, align: int = 4096, record_cap: int = 1024, total_bytes: int | None = None,
+                      stream=None):
+    """Walk and verify every record of the manifest images held in the device
+    tensor base -> (reports (MANIFEST_REPORT_DTYPE, one per image), summary
+    (one MANIFEST_SUMMARY_DTYPE record), the n_listed records
+    (MANIFEST_RECORD_DTYPE)).  img_off / img_size may be device tensors or host
+    sequences.  Waits for the stream.  With an invalid layout
+    (summary["invalid_image"] set) reports and records come back empty."""
+    def dev(x):
+        if isinstance(x, torch.Tensor):
+            return x
+        return torch.from_numpy(np.ascontiguousarray(x, dtype=np.uint64).view(np.int64)).to(base.device)
+    img_off, img_size = dev(img_off), dev(img_size)
+    n = img_off.numel()
+    reports, summary, records = manifest_scan_async(base, img_off, img_size, align, total_bytes, n, None, None, None,
+                                                    record_cap, stream)
+    if stream is not None:  # the copies below are ordered on torch's current stream only
+        _call("pcs_synchronize", _stream(stream))
+    s = np.ascontiguousarray(summary.cpu().numpy()).view(np.uint64).view(MANIFEST_SUMMARY_DTYPE)[0]
+    if int(s["invalid_image"]) != NO_PAGE:
+        return np.zeros(0, dtype=MANIFEST_REPORT_DTYPE), s, np.zeros(0, dtype=MANIFEST_RECORD_DTYPE)
+    reps = np.ascontiguousarray(reports[:n].cpu().numpy()).view(np.uint64).view(MANIFEST_REPORT_DTYPE).reshape(-1)
+    listed = int(s["n_listed"])
+    recs = (np.ascontiguousarray(records[:listed].cpu().numpy()).view(np.uint8).view(MANIFEST_RECORD_DTYPE).reshape(-1)
+            if listed else np.zeros(0, dtype=MANIFEST_RECORD_DTYPE))
+    return reps, s, recs
+
+
+def manifest_scan_host(images: list, align: int = 4096, record_cap: int = 1024):
+    """pcs_manifest_scan_host over whole manifest images in host memory (bytes,
+    bytearray, memoryview or uint8 numpy arrays, any alignment) -> (reports,
+    summary, records) as manifest_scan_dev."""
+    n = len(images)
+    views = [np.frombuffer(b, dtype=np.uint8) if not isinstance(b, np.ndarray) else b for b in images]
+    ptrs = np.array([v.ctypes.data if v.size else 0 for v in views], dtype=np.uint64)
+    sizes = np.array([v.size for v in views], dtype=np.uint64)
+    reports = np.zeros(max(1, n), dtype=MANIFEST_REPORT_DTYPE)
+    summary = np.zeros(1, dtype=MANIFEST_SUMMARY_DTYPE)
+    records = np.zeros(max(1, record_cap), dtype=MANIFEST_RECORD_DTYPE)
+    _call("pcs_manifest_scan_host", ptrs.ctypes.data, sizes.ctypes.data, n, align, reports.ctypes.data,
+          summary.ctypes.data, records.ctypes.data if record_cap else 0, record_cap)
+    return reports[:n], summary[0], records[: int(summary[0]["n_listed"])]
 
 
 class Batch:

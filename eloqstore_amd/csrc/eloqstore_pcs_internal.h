@@ -67,6 +67,17 @@ hipError_t run_flip(uint8_t* pages, uint64_t page_size, uint64_t n, uint64_t eve
                     hipStream_t s);
 // ManifestBuilder::CalcChecksum over a device-resident content buffer
 hipError_t run_manifest(const uint8_t* content, uint64_t len, uint64_t* out, hipStream_t s);
+// Manifest scan over n_images images [base + off[i], + size[i]) inside [base,
+// base + total): off and size are device words, checked on the device; align
+// is a power of two in [64, 65536] and base 8-byte aligned (the caller checks
+// both).  reports = 12 words per image (pcs_manifest_report), summary = the 12
+// words of pcs_manifest_summary, records[0 .. min(n_records, cap)) = 5 words
+// each (pcs_manifest_record), in walk order with the images in order.  All
+// device memory; enqueues on s and never waits.  hipErrorInvalidValue when
+// total / align + n_images + total / 2^20 does not fit 31 bits.
+hipError_t run_manifest_scan(const uint8_t* base, uint64_t total, const uint64_t* off, const uint64_t* size,
+                             uint64_t n_images, uint32_t align, uint64_t* reports, uint64_t* summary,
+                             uint64_t* records, uint64_t cap, hipStream_t s);
 // Event-fenced device scratch (see ScratchPool in pcs_kernels.hip): the
 // buffer is reused only after the work queued on `s` at release completes.
 hipError_t scratch_acquire(size_t bytes, void** out, int* id);

@@ -187,6 +187,58 @@ FilesReport ScrubFiles(std::span<const char* const> pages, size_t page_size, uin
     return report;
 }
 
+int TryScanManifests(std::span<const std::string_view> images, ManifestsReport& report, uint32_t align,
+                     size_t max_records) {
+    static_assert(sizeof(ManifestRecord) == sizeof(pcs_manifest_record), "ManifestRecord mirrors pcs_manifest_record");
+    const size_t n = images.size();
+    std::vector<const void*> ptrs(n);
+    std::vector<uint64_t> sizes(n);
+    for (size_t i = 0; i < n; ++i) {
+        ptrs[i] = images[i].data();
+        sizes[i] = images[i].size();
+    }
+    std::vector<pcs_manifest_report> reports(n);
+    std::vector<pcs_manifest_record> records(max_records);
+    pcs_manifest_summary sum{};
+    const int rc = pcs_manifest_scan_host(ptrs.data(), sizes.data(), n, align, reports.data(), &sum, records.data(),
+                                          max_records);
+    if (rc != PCS_OK) return rc;
+    report.manifests.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+        const pcs_manifest_report& r = reports[i];
+        ManifestReport& o = report.manifests[i];
+        o.size = r.size;
+        o.n_records = r.n_records;
+        o.n_ok = r.n_ok;
+        o.n_corrupt = r.n_corrupt;
+        o.first_corrupt = r.first_corrupt;
+        o.n_ok_after_corrupt = r.n_ok_after_corrupt;
+        o.valid_prefix_bytes = r.valid_prefix_bytes;
+        o.end_offset = r.end_offset;
+        o.end_reason = static_cast<ManifestEnd>(r.end_reason);
+        o.verdict = static_cast<ManifestVerdict>(r.verdict);
+        o.first_record = r.first_record;
+        o.max_record_bytes = r.max_record_bytes;
+    }
+    report.n_records = sum.n_records;
+    report.n_ok = sum.n_ok;
+    report.n_corrupt = sum.n_corrupt;
+    for (int k = 0; k < 5; ++k) report.n_by_verdict[k] = sum.n_by_verdict[k];
+    report.first_bad_manifest = sum.first_bad_image;
+    report.records.resize(sum.n_listed);
+    for (size_t k = 0; k < sum.n_listed; ++k) {
+        const pcs_manifest_record& r = records[k];
+        report.records[k] = ManifestRecord{r.offset, r.stored, r.computed, r.payload_len, r.root, r.ttl_root, r.ok};
+    }
+    return PCS_OK;
+}
+
+ManifestsReport ScanManifests(std::span<const std::string_view> images, uint32_t align, size_t max_records) {
+    ManifestsReport report;
+    if (int rc = TryScanManifests(images, report, align, max_records)) die("ScanManifests", rc);
+    return report;
+}
+
 void RegisterPagePool(void* base, size_t bytes) {
     if (int rc = pcs_host_register(base, bytes)) die("RegisterPagePool", rc);
 }

@@ -9,6 +9,7 @@
 #include "region_registry.h"
 #include "extent_merge.h"
 #include "file_merge.h"
+#include "manifest_scan.h"
 #include "scrub_merge.h"
 
 #include <hip/hip_runtime.h>
@@ -1480,6 +1481,65 @@ int manifest_host(const void* content, uint64_t len, uint64_t* out) {
     return finish(e, "manifest checksum");
 }
 
+// pcs_manifest_scan_host: whole images in staging groups (manifest_pack),
+// each copied into the thread's pinned staging at multiples of align, DMA'd
+// and scanned by the device form; reports and the listed records come back per
+// group, first_record and the summary are built over the whole batch.
+int host_manifest_scan(const void* const* images, const uint64_t* sizes, uint64_t n_images, uint32_t align,
+                       pcs_manifest_report* reports, pcs_manifest_summary* summary, pcs_manifest_record* records,
+                       uint64_t record_cap) {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return hip_fail(e, "hipGetDevice");
+    Slot& slot = t_ctx[dev].slot[0];  // the calling thread's stream and staging on this device
+    uint64_t listed = 0;              // records written so far
+    for (const pcs::ManifestGroup& g : pcs::manifest_pack(sizes, n_images, align)) {
+        if (!pcs::manifest_batch_fits(g.bytes, g.count, align)) return fail(PCS_ERR_INVALID, "a group of images is too large");
+        if (int rc = ensure_slot(slot, std::max<uint64_t>(g.bytes, 1), 1)) return rc;
+        hipStream_t s = slot.stream;
+        for (uint64_t k = 0; k < g.count; ++k)
+            if (sizes[g.first + k]) std::memcpy(slot.h_pages + g.off[k], images[g.first + k], sizes[g.first + k]);
+        // the records this group can list: what the cap leaves, at most a record per slot
+        const uint64_t cap = std::min<uint64_t>(record_cap - listed, g.bytes / align + g.count);
+        void* buf = nullptr;
+        int id = -1;
+        e = pcs::scratch_acquire(g.count * (16 + sizeof(pcs_manifest_report)) + sizeof(pcs_manifest_summary) +
+                                     cap * sizeof(pcs_manifest_record),
+                                 &buf, &id);
+        uint64_t* d_off = static_cast<uint64_t*>(buf);
+        uint64_t* d_size = d_off + g.count;
+        pcs_manifest_report* d_rep = reinterpret_cast<pcs_manifest_report*>(d_size + g.count);
+        pcs_manifest_summary* d_sum = reinterpret_cast<pcs_manifest_summary*>(d_rep + g.count);
+        pcs_manifest_record* d_rec = reinterpret_cast<pcs_manifest_record*>(d_sum + 1);
+        pcs_manifest_summary sum{};
+        if (e == hipSuccess && g.bytes) e = hipMemcpyAsync(slot.d_pages, slot.h_pages, g.bytes, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_off, g.off.data(), g.count * 8, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_size, sizes + g.first, g.count * 8, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess)
+            e = pcs::run_manifest_scan(slot.d_pages, g.bytes, d_off, d_size, g.count, align,
+                                       reinterpret_cast<uint64_t*>(d_rep), reinterpret_cast<uint64_t*>(d_sum),
+                                       reinterpret_cast<uint64_t*>(cap ? d_rec : nullptr), cap, s);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(reports + g.first, d_rep, g.count * sizeof(pcs_manifest_report), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(&sum, d_sum, sizeof(sum), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e == hipSuccess && sum.invalid_image != UINT64_MAX) e = hipErrorUnknown;  // the plan's own layout
+        if (e == hipSuccess && sum.n_listed) {
+            e = hipMemcpyAsync(records + listed, d_rec, sum.n_listed * sizeof(pcs_manifest_record),
+                               hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+            listed += sum.n_listed;
+        }
+        if (id >= 0) (void)pcs::scratch_release(id, s);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(s);  // nothing of this call left in flight
+            return finish(e, "manifest scan");
+        }
+    }
+    pcs::manifest_summarize(reports, n_images, record_cap, summary);
+    return PCS_OK;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -2270,6 +2330,49 @@ int pcs_manifest_validate_host(const void* record, uint64_t size, int* valid) {
     std::memcpy(&stored, record, 8);  // DecodeFixed64
     *valid = stored == h ? 1 : 0;
     return PCS_OK;
+}
+
+int pcs_manifest_scan_dev(const void* d_base, uint64_t total_bytes, const uint64_t* d_img_off,
+                          const uint64_t* d_img_size, uint64_t n_images, uint32_t align, pcs_manifest_report* d_reports,
+                          pcs_manifest_summary* d_summary, pcs_manifest_record* d_records, uint64_t record_cap,
+                          pcs_stream_t stream) {
+    static_assert(sizeof(pcs_manifest_record) == 40, "pcs_manifest_record is 40 bytes");
+    static_assert(sizeof(pcs_manifest_report) == 12 * sizeof(uint64_t), "pcs_manifest_report is 12 x u64");
+    static_assert(sizeof(pcs_manifest_summary) == 12 * sizeof(uint64_t), "pcs_manifest_summary is 12 x u64");
+    if (int rc = require_device()) return rc;
+    if (!d_summary) return fail(PCS_ERR_INVALID, "d_summary is null");
+    if (!pcs::manifest_align_ok(align)) return fail(PCS_ERR_INVALID, "align must be a power of two in [64, 65536]");
+    if (total_bytes && !d_base) return fail(PCS_ERR_INVALID, "d_base is null");
+    if (reinterpret_cast<uintptr_t>(d_base) % 8) return fail(PCS_ERR_INVALID, "d_base is not 8-byte aligned");
+    if (n_images && (!d_img_off || !d_img_size)) return fail(PCS_ERR_INVALID, "d_img_off / d_img_size is null");
+    if (n_images && !d_reports) return fail(PCS_ERR_INVALID, "d_reports is null");
+    if (record_cap && !d_records) return fail(PCS_ERR_INVALID, "d_records is null with record_cap > 0");
+    if (reinterpret_cast<uintptr_t>(d_records) % 8) return fail(PCS_ERR_INVALID, "d_records is not 8-byte aligned");
+    if (!pcs::manifest_batch_fits(total_bytes, n_images, align))
+        return fail(PCS_ERR_INVALID, "total_bytes / align + n_images + total_bytes / 2^20 must stay below 2^31");
+    return finish(pcs::run_manifest_scan(static_cast<const uint8_t*>(d_base), total_bytes, d_img_off, d_img_size,
+                                         n_images, align, reinterpret_cast<uint64_t*>(d_reports),
+                                         reinterpret_cast<uint64_t*>(d_summary), reinterpret_cast<uint64_t*>(d_records),
+                                         record_cap, reinterpret_cast<hipStream_t>(stream)),
+                  "manifest scan kernel launch");
+}
+
+int pcs_manifest_scan_host(const void* const* images, const uint64_t* sizes, uint64_t n_images, uint32_t align,
+                           pcs_manifest_report* reports, pcs_manifest_summary* summary, pcs_manifest_record* records,
+                           uint64_t record_cap) {
+    if (!summary) return fail(PCS_ERR_INVALID, "summary is null");
+    if (!pcs::manifest_align_ok(align)) return fail(PCS_ERR_INVALID, "align must be a power of two in [64, 65536]");
+    if (n_images && (!images || !sizes)) return fail(PCS_ERR_INVALID, "images / sizes is null");
+    if (n_images && !reports) return fail(PCS_ERR_INVALID, "reports is null");
+    if (record_cap && !records) return fail(PCS_ERR_INVALID, "records is null with record_cap > 0");
+    if (n_images >= (1ull << 31)) return fail(PCS_ERR_INVALID, "too many images");
+    for (uint64_t i = 0; i < n_images; ++i) {
+        if (sizes[i] && !images[i]) return fail(PCS_ERR_INVALID, "an image of non-zero size is null");
+        if (!pcs::manifest_batch_fits(sizes[i] + align, 1, align)) return fail(PCS_ERR_INVALID, "an image is too large");
+    }
+    if (injected_failure()) return fail(PCS_ERR_HIP, "injected failure (PCS_TUNE_FAIL_INJECT)");
+    if (int rc = require_device()) return rc;
+    return host_manifest_scan(images, sizes, n_images, align, reports, summary, records, record_cap);
 }
 
 int pcs_shard_range(uint64_t n, int world, int rank, uint64_t* begin, uint64_t* end) {

@@ -957,53 +957,60 @@ __device__ __forceinline__ uint64_t xxh3_long_block(const uint64_t* __restrict__
     return T;
 }
 
+// One long range (xxh3_long_ok) by the whole 256-thread workgroup: *out =
+// XXH3_64bits(in8, L).  S is the workgroup's window of block sums.
+__device__ __forceinline__ void xxh3_long_range(uint64_t (*S)[8], const uint8_t* __restrict__ in8, uint32_t L,
+                                                uint64_t* __restrict__ out) {
+    const int tid = threadIdx.x, g = tid & 15, grp = tid >> 4;
+    const uint64_t* in = reinterpret_cast<const uint64_t*>(in8);
+    const uint32_t nb = (L - 1) / 1024;
+    uint64_t acc = tid < 8 ? c_init_acc[tid] : 0;  // threads 0..7 own acc[tid]
+    for (uint32_t w0 = 0; w0 < nb; w0 += kLongWin) {
+        const int nw = (int)min((uint32_t)kLongWin, nb - w0);
+#pragma unroll
+        for (int i = 0; i < kLongWin / 16; ++i) {
+            const int b = grp + 16 * i;
+            if (b < nw) {
+                const uint64_t T = xxh3_long_block(in + (size_t)(w0 + b) * 128, g, 16);
+                if (g < 8) S[b][g] = T;
+            }
+        }
+        __syncthreads();
+        if (tid < 8)
+            for (int b = 0; b < nw; ++b) acc = xxh3_scramble(acc + S[b][tid], c_keys.scr[tid]);
+        __syncthreads();
+    }
+    if (grp == 0) {
+        const int nst = (int)(((L - 1) - 1024 * nb) / 64);
+        uint64_t T = xxh3_long_block(in + (size_t)nb * 128, g, nst);
+        // last stripe at input + L - 64, keyed with secret + 121 (xxhash.h:6013-6015)
+        uint64_t M = 0, R = 0;
+        if (g < 8) {
+            const uint64_t v = ld64(in8 + L - 64 + 8 * g);
+            M = mul32x32(v ^ c_keys.last[g]);
+            R = v;
+        }
+        T += M + dpp64<kQuadSwap1>(R);
+        acc += T;
+        // mergeAccs (xxhash.h:6029-6052): even lanes fold pairs (l, l + 1)
+        const uint64_t nxt = dpp64<kRowRor15>(acc);
+        uint64_t m = (g < 8 && (g & 1) == 0) ? mul_fold64(acc ^ c_keys.merge[g], nxt ^ c_keys.merge[g + 1]) : 0;
+        m += dpp64<kRowRor2>(m);
+        m += dpp64<kRowRor4>(m);  // lane 0..7: m0+m2+m4+m6 (lanes 0,2,4,6 of 0..7)
+        if (g == 6) *out = xxh3_avalanche((uint64_t)L * kP64_1 + m);
+    }
+    __syncthreads();
+}
+
 __global__ __launch_bounds__(256) void k_xxh3_long(const uint8_t* __restrict__ base, const uint64_t* __restrict__ off,
                                                   const uint32_t* __restrict__ len, uint64_t n,
                                                   uint64_t* __restrict__ out) {
     __shared__ uint64_t S[kLongWin][8];
-    const int tid = threadIdx.x, g = tid & 15, grp = tid >> 4;
     for (uint64_t r = blockIdx.x; r < n; r += gridDim.x) {
         const uint8_t* in8 = base + off[r];
         const uint32_t L = len[r];
         if (!xxh3_long_ok(in8, L)) continue;  // uniform over the workgroup
-        const uint64_t* in = reinterpret_cast<const uint64_t*>(in8);
-        const uint32_t nb = (L - 1) / 1024;
-        uint64_t acc = tid < 8 ? c_init_acc[tid] : 0;  // threads 0..7 own acc[tid]
-        for (uint32_t w0 = 0; w0 < nb; w0 += kLongWin) {
-            const int nw = (int)min((uint32_t)kLongWin, nb - w0);
-#pragma unroll
-            for (int i = 0; i < kLongWin / 16; ++i) {
-                const int b = grp + 16 * i;
-                if (b < nw) {
-                    const uint64_t T = xxh3_long_block(in + (size_t)(w0 + b) * 128, g, 16);
-                    if (g < 8) S[b][g] = T;
-                }
-            }
-            __syncthreads();
-            if (tid < 8)
-                for (int b = 0; b < nw; ++b) acc = xxh3_scramble(acc + S[b][tid], c_keys.scr[tid]);
-            __syncthreads();
-        }
-        if (grp == 0) {
-            const int nst = (int)(((L - 1) - 1024 * nb) / 64);
-            uint64_t T = xxh3_long_block(in + (size_t)nb * 128, g, nst);
-            // last stripe at input + L - 64, keyed with secret + 121 (xxhash.h:6013-6015)
-            uint64_t M = 0, R = 0;
-            if (g < 8) {
-                const uint64_t v = ld64(in8 + L - 64 + 8 * g);
-                M = mul32x32(v ^ c_keys.last[g]);
-                R = v;
-            }
-            T += M + dpp64<kQuadSwap1>(R);
-            acc += T;
-            // mergeAccs (xxhash.h:6029-6052): even lanes fold pairs (l, l + 1)
-            const uint64_t nxt = dpp64<kRowRor15>(acc);
-            uint64_t m = (g < 8 && (g & 1) == 0) ? mul_fold64(acc ^ c_keys.merge[g], nxt ^ c_keys.merge[g + 1]) : 0;
-            m += dpp64<kRowRor2>(m);
-            m += dpp64<kRowRor4>(m);  // lane 0..7: m0+m2+m4+m6 (lanes 0,2,4,6 of 0..7)
-            if (g == 6) out[r] = xxh3_avalanche((uint64_t)L * kP64_1 + m);
-        }
-        __syncthreads();
+        xxh3_long_range(S, in8, L, out + r);
     }
 }
 
@@ -1893,7 +1900,7 @@ uint64_t next_call_id() {
 // tuning knobs (pcs_set_tuning): read at every launch
 // ---------------------------------------------------------------------------
 namespace {
-constexpr int kTuneKeys = 37;
+constexpr int kTuneKeys = 39;
 // Keys retired in round 2 with the variants they selected (measured slower,
 // DESIGN.md §4): 4 XXH64 nt loads, 5 in-place stamp width, 10 descriptor tile
 // sort, 12 descriptor slices, 14 XXH64 descriptor sort; round-2 experiments
@@ -1911,7 +1918,7 @@ constexpr int kTuneKeys = 37;
 constexpr bool kRetired[kTuneKeys] = {false, false, false, false, true, true, false, false, false, false, true,  false,
                                       true,  false, true,  false, true,  true,  true,  true,  true,  true,  true,  false,
                                       false, true,  false, false, false, true,  false, false, true,  false,
-                                      false, false, false};
+                                      false, false, false, /*37: never assigned*/ true, false};
 std::atomic<int64_t> g_tune[kTuneKeys] = {0, /*xxh3 blocks/CU*/ 0, /*xxh64 blocks/CU*/ 0, /*xxh3 nt*/ 1,
                                           /*retired*/ 0, /*retired*/ 0, /*xxh64 LDS depth (2/3/4/5 -> 1/2/4/3)*/ 0,
                                           /*zero copy*/ 1, /*xxh3 run-time size: 4-block batches*/ 1,
@@ -1939,7 +1946,9 @@ std::atomic<int64_t> g_tune[kTuneKeys] = {0, /*xxh3 blocks/CU*/ 0, /*xxh64 block
                                           /*test only: service kernels serve nothing and leave this many us late*/ 0,
                                           /*zero-copy batches completing from their verdicts: event behind the kernel*/ 0,
                                           /*sync host calls: microseconds of spinning before sleeping between checks (0 = spin)*/ 0,
-                                          /*validate service: polls read the kernel's departure words*/ 1};
+                                          /*validate service: polls read the kernel's departure words*/ 1,
+                                          /*never assigned*/ 0,
+                                          /*manifest scan: slots per LDS tile of the walk (power of two, 64..4096)*/ 2048};
 }
 int set_tuning(int key, int64_t value) {
     if (key <= 0 || key >= kTuneKeys || kRetired[key] || value < 0) return -1;
@@ -2520,6 +2529,554 @@ hipError_t run_files(const uint8_t* cls, const uint8_t* type, uint64_t n, const 
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     hipLaunchKernelGGL(k_files_summary, dim3(1), dim3(256), 0, s, n_files, status, reports, flags, cap, list, summary);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Manifest scan (pcs_manifest_scan_dev): walk and verify every record of many
+// manifest images (Replayer::ParseNextRecord, src/replayer.cpp:74-140).  Image
+// i is [base + off[i], + size[i]); a record is checksum(8) | root(4) |
+// ttl_root(4) | payload_len(4) | payload, padded to `align`.  Offsets and sizes
+// are a device array, so nothing here may trust them.  Nine launches ordered by
+// construction (the one atomic on global memory adds up a count, so the output
+// is the same on every call):
+//   k_mscan_layout  one block: checks every image against the layout rules and
+//                   scans the images' slot counts ceil(size / align) into
+//                   slot_base.  The first invalid image goes into ctl[0];
+//                   every later kernel leaves at once when it is set, so no
+//                   address is ever formed from an unchecked offset;
+//   k_mscan_slots   one lane per align-slot of every image, each a candidate
+//                   record start: the header bounds test and one aligned 4-byte
+//                   load of payload_len, the only image bytes the walk needs,
+//                   all independent.  Writes the slot's word (the next slot, or
+//                   an end code) and its payload_len;
+//   k_mscan_walk    one wave per image: tiles of the slot words and lengths
+//                   pass through LDS and the chain is followed there, never
+//                   through the image, 64 slots at a time: runs of one-slot
+//                   records in one scalar step, any other record by a
+//                   readlane; a record whose next slot lies tiles ahead moves
+//                   the tile window straight to it.  The records met in a tile
+//                   are noted in LDS in walk order; the wave then takes their
+//                   chunk counts ceil((12 + len) / 1 MiB) and scans them, so
+//                   every record gets its ordinal and its image-local first
+//                   chunk;
+//   k_mscan_plan    one block: exclusive sums of the images' record and chunk
+//                   counts (first_record, first_chunk);
+//   k_mscan_emit    one lane per record: (offset, length) of each of its chunks,
+//                   offsets in the page convention (content 8 bytes on), and
+//                   the number of chunks of kLongMin bytes and more;
+//   k_mscan_hash    one 16-lane group per chunk shorter than kLongMin: the
+//                   any-size group body from 241 content bytes up, xxh3_short
+//                   on the group's first lane below;
+//   k_mscan_long    a workgroup per chunk of kLongMin bytes and more, the 1 MiB
+//                   chunks of snapshots (k_xxh3_long's body); leaves at once
+//                   when the batch has none;
+//   k_mscan_report  one block per image, a lane per record: folds the chunk
+//                   digests, compares, writes the record entry below the cap
+//                   and reduces the image's report;
+//   k_mscan_summary one block: totals, verdict census, first bad image.
+// ---------------------------------------------------------------------------
+constexpr int kMscanReportWords = 12;   // pcs_manifest_report
+constexpr int kMscanSummaryWords = 12;  // pcs_manifest_summary
+constexpr int kMscanRecordWords = 5;    // pcs_manifest_record: offset, stored, computed, len | root, ttl_root | ok
+constexpr uint64_t kMscanHeader = 20;   // checksum(8) root(4) ttl_root(4) payload_len(4)
+// slot words above every slot index: why the chain ends at this slot
+constexpr uint32_t kSlotShortHeader = 0xFFFFFFF1u;   // fewer than 20 bytes left: no record
+constexpr uint32_t kSlotShortPayload = 0xFFFFFFF2u;  // the payload runs past the image: no record
+constexpr uint32_t kSlotLastPadding = 0xFFFFFFF3u;   // a record, its padding cut by the end of the image
+constexpr uint32_t kSlotLastClean = 0xFFFFFFF0u;     // a record that ends the image exactly
+constexpr int kMscanCtlWords = 8;  // ctl: invalid image, slots, records, chunks, long chunks
+constexpr int kMscanMaxTile = 4096;
+
+// the image that holds global slot (or record position) j: the last i with slot_base[i] <= j
+__device__ __forceinline__ uint64_t mscan_image_of(const uint64_t* __restrict__ slot_base, uint64_t n_images, uint64_t j) {
+    uint64_t lo = 0, hi = n_images;
+    while (hi - lo > 1) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (slot_base[mid] <= j) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(256) void k_mscan_layout(const uint64_t* __restrict__ off, const uint64_t* __restrict__ size,
+                                                     uint64_t n_images, uint64_t total, uint32_t shift,
+                                                     uint64_t* __restrict__ slot_base, uint64_t* __restrict__ ctl) {
+    __shared__ uint64_t w4[4];
+    __shared__ unsigned long long bad;
+    if (threadIdx.x == 0) bad = ~0ull;
+    __syncthreads();
+    const uint64_t mask = (1ull << shift) - 1;
+    uint64_t slots = 0;  // slots of the images before this round (uniform)
+    for (uint64_t base = 0; base < n_images; base += 256) {
+        const uint64_t i = base + threadIdx.x;
+        uint64_t c = 0;
+        if (i < n_images) {
+            const uint64_t o = off[i], sz = size[i];
+            bool ok = (o & mask) == 0 && o <= total && sz <= total - o;
+            if (ok && i > 0) {
+                const uint64_t po = off[i - 1], ps = size[i - 1];
+                // the predecessor's own check makes po + ps <= total when it is valid; when it
+                // is not, the whole layout is invalid whatever this comparison gives
+                ok = po <= total && ps <= total - po && o >= ((po + ps + mask) & ~mask);
+            }
+            if (!ok) atomicMin(&bad, (unsigned long long)i);
+            else c = (sz + mask) >> shift;
+        }
+        uint64_t t;
+        const uint64_t before = slots + block_excl_scan(c, w4, t);
+        if (i < n_images) slot_base[i] = before;
+        slots += t;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        slot_base[n_images] = slots;
+        ctl[0] = bad;
+        ctl[1] = bad == ~0ull ? slots : 0;
+        ctl[2] = 0;
+        ctl[3] = 0;
+        ctl[4] = 0;  // k_mscan_emit counts the long chunks here
+    }
+}
+
+__global__ __launch_bounds__(256) void k_mscan_slots(const uint8_t* __restrict__ base, const uint64_t* __restrict__ off,
+                                                    const uint64_t* __restrict__ size, uint64_t n_images,
+                                                    uint32_t shift, const uint64_t* __restrict__ slot_base,
+                                                    const uint64_t* __restrict__ ctl, uint32_t* __restrict__ slot_next,
+                                                    uint32_t* __restrict__ slot_len) {
+    if (ctl[0] != ~0ull) return;
+    const uint64_t n_slots = ctl[1];
+    const uint64_t mask = (1ull << shift) - 1;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n_slots; j += stride) {
+        const uint64_t i = mscan_image_of(slot_base, n_images, j);
+        const uint64_t o = (j - slot_base[i]) << shift, sz = size[i];
+        const uint64_t left = sz - o;  // >= 1: slot s exists only for s * align < size
+        uint32_t next = kSlotShortHeader, len = 0;
+        if (left >= kMscanHeader) {
+            // base is 8-byte aligned, off[i] and o multiples of align >= 64: an aligned word
+            len = *reinterpret_cast<const uint32_t*>(base + off[i] + o + 16);
+            const uint64_t need = kMscanHeader + (uint64_t)len;
+            if (need > left) {
+                next = kSlotShortPayload;
+            } else {
+                const uint64_t o2 = (o + need + mask) & ~mask;
+                next = o2 > sz ? kSlotLastPadding : o2 == sz ? kSlotLastClean : (uint32_t)(o2 >> shift);
+            }
+        }
+        slot_next[j] = next;
+        slot_len[j] = len;
+    }
+}
+
+__device__ __forceinline__ uint64_t wave_excl_scan(uint64_t v, uint64_t& total) {
+    const int lane = threadIdx.x & 63;
+    uint64_t incl = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t t = __shfl_up((unsigned long long)incl, d, 64);
+        if (lane >= d) incl += t;
+    }
+    total = __shfl((unsigned long long)incl, 63, 64);
+    return incl - v;
+}
+
+// img: 4 words per image: records, chunks, end offset, end reason
+__global__ __launch_bounds__(64) void k_mscan_walk(const uint64_t* __restrict__ size, uint64_t n_images, uint32_t shift,
+                                                  uint32_t tile, const uint64_t* __restrict__ slot_base,
+                                                  const uint64_t* __restrict__ ctl,
+                                                  const uint32_t* __restrict__ slot_next,
+                                                  const uint32_t* __restrict__ slot_len, uint32_t* __restrict__ rec_slot,
+                                                  uint32_t* __restrict__ rec_chunk, uint64_t* __restrict__ img) {
+    extern __shared__ uint32_t mscan_lds[];  // the tile's slot words and lengths, then its records' slots in walk order
+    if (ctl[0] != ~0ull) return;
+    uint32_t* t_next = mscan_lds;
+    uint32_t* t_len = mscan_lds + tile;
+    uint32_t* t_rec = mscan_lds + 2 * tile;
+    const uint64_t i = blockIdx.x;
+    const int lane = threadIdx.x;
+    const uint64_t sb = slot_base[i];
+    const uint32_t ns = (uint32_t)(slot_base[i + 1] - sb);
+    const uint64_t sz = size[i];
+    uint32_t cur = 0;  // the slot the chain stands on (uniform)
+    uint64_t n_rec = 0, n_chunks = 0, end_off = 0, reason = 0;  // size 0: END_CLEAN at 0
+    bool done = ns == 0;
+    while (!done) {
+        const uint32_t t0 = cur & ~(tile - 1);  // the tile that holds cur, however far the last record reached
+        const uint32_t cnt = min(tile, ns - t0);
+        for (uint32_t k0 = 0; k0 < cnt; k0 += 64 * 8) {  // eight loads of each array in flight per lane
+            uint32_t a[8], b[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const uint32_t k = k0 + 64 * j + lane;
+                a[j] = k < cnt ? slot_next[sb + t0 + k] : 0;
+                b[j] = k < cnt ? slot_len[sb + t0 + k] : 0;
+            }
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const uint32_t k = k0 + 64 * j + lane;
+                if (k < cnt) {
+                    t_next[k] = a[j];
+                    t_len[k] = b[j];
+                }
+            }
+        }
+        __syncthreads();
+        // The chain is followed 64 slots at a time: each lane takes one slot word of
+        // the window from LDS and the walk inside the window is scalar.  `seq` marks
+        // the lanes whose record ends inside its own slot (next == slot + 1): a run
+        // of them is taken in one step, any other record with one readlane.  (A walk
+        // that read LDS once per record took 130 ns a step, 270 of the 332 us of an
+        // 8 MiB image of one-slot records)  A slot word is an
+        // end code, all of which lie above every slot index, or a slot index above
+        // cur and below ns.  The window's records are the set bits of `hit`,
+        // ascending as the chain is.
+        uint32_t m = 0;
+        while (!done && cur < t0 + cnt) {
+            const uint32_t w0 = cur & ~63u;  // tiles are multiples of 64 slots
+            const uint32_t k = w0 - t0 + lane;
+            const uint32_t mine = k < cnt ? t_next[k] : kSlotShortHeader;
+            const uint64_t seq = __ballot(mine == w0 + lane + 1);
+            const uint32_t wend = min(w0 + 64, t0 + cnt);
+            uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)cur);
+            uint64_t hit = 0;
+            while (c < wend) {
+                const uint32_t p = c - w0;
+                const uint64_t stop = ~(seq >> p);  // the shift leaves zeros above bit 63 - p: they stop a run
+                const uint32_t run = stop ? (uint32_t)__builtin_ctzll(stop) : 64u;
+                if (run) {
+                    hit |= (run == 64 ? ~0ull : (1ull << run) - 1) << p;
+                    c += run;
+                    continue;
+                }
+                const uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)mine, (int)p);
+                if (w == kSlotShortHeader || w == kSlotShortPayload) {
+                    done = true;
+                    end_off = (uint64_t)c << shift;
+                    reason = w == kSlotShortHeader ? 1 : 2;
+                    break;
+                }
+                hit |= 1ull << p;
+                if (w == kSlotLastClean || w == kSlotLastPadding) {
+                    done = true;
+                    end_off = sz;
+                    reason = w == kSlotLastClean ? 0 : 3;
+                    break;
+                }
+                c = w;
+            }
+            cur = c;
+            if ((hit >> lane) & 1) t_rec[m + __builtin_popcountll(hit & ((1ull << lane) - 1))] = w0 + lane;
+            m += (uint32_t)__builtin_popcountll(hit);
+        }
+        __syncthreads();
+        for (uint32_t q0 = 0; q0 < m; q0 += 64) {  // the tile's records, 64 at a time in walk order
+            const uint32_t q = q0 + lane;
+            uint32_t slot = 0;
+            uint64_t nc = 0;
+            if (q < m) {
+                slot = t_rec[q];
+                nc = (12ull + t_len[slot - t0] + (kManifestChunk - 1)) >> 20;
+            }
+            uint64_t t;
+            const uint64_t before = wave_excl_scan(nc, t);
+            if (q < m) {
+                rec_slot[sb + n_rec + q] = slot;
+                rec_chunk[sb + n_rec + q] = (uint32_t)(n_chunks + before);
+            }
+            n_chunks += t;
+        }
+        n_rec += m;
+        __syncthreads();  // the tile arrays are refilled by the next tile
+    }
+    if (lane == 0) {
+        img[4 * i + 0] = n_rec;
+        img[4 * i + 1] = n_chunks;
+        img[4 * i + 2] = end_off;
+        img[4 * i + 3] = reason;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_mscan_plan(uint64_t n_images, const uint64_t* __restrict__ img,
+                                                   uint64_t* __restrict__ first_rec, uint64_t* __restrict__ first_chunk,
+                                                   uint64_t* __restrict__ ctl) {
+    __shared__ uint64_t w4[4];
+    if (ctl[0] != ~0ull) return;
+    uint64_t recs = 0, chunks = 0;  // of the images before this round (uniform)
+    for (uint64_t base = 0; base < n_images; base += 256) {
+        const uint64_t i = base + threadIdx.x;
+        const uint64_t r = i < n_images ? img[4 * i] : 0, c = i < n_images ? img[4 * i + 1] : 0;
+        uint64_t tr, tc;
+        const uint64_t br = recs + block_excl_scan(r, w4, tr);
+        __syncthreads();
+        const uint64_t bc = chunks + block_excl_scan(c, w4, tc);
+        if (i < n_images) {
+            first_rec[i] = br;
+            first_chunk[i] = bc;
+        }
+        recs += tr;
+        chunks += tc;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        ctl[2] = recs;
+        ctl[3] = chunks;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_mscan_emit(const uint64_t* __restrict__ off, uint64_t n_images, uint32_t shift,
+                                                   const uint64_t* __restrict__ slot_base,
+                                                   const uint64_t* __restrict__ ctl, const uint64_t* __restrict__ img,
+                                                   const uint64_t* __restrict__ first_chunk,
+                                                   const uint32_t* __restrict__ slot_len,
+                                                   const uint32_t* __restrict__ rec_slot,
+                                                   const uint32_t* __restrict__ rec_chunk,
+                                                   uint64_t* __restrict__ chunk_off, uint32_t* __restrict__ chunk_len,
+                                                   unsigned long long* __restrict__ n_long) {
+    if (ctl[0] != ~0ull) return;
+    const uint64_t n_slots = ctl[1];
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    uint64_t longs = 0;  // this lane's chunks of kLongMin bytes and more
+    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n_slots; j += stride) {
+        const uint64_t i = mscan_image_of(slot_base, n_images, j);
+        const uint64_t sb = slot_base[i];
+        if (j - sb >= img[4 * i]) continue;  // positions past the image's records
+        const uint32_t slot = rec_slot[j];
+        const uint64_t content = 12ull + slot_len[sb + slot];
+        const uint64_t rec = off[i] + ((uint64_t)slot << shift);
+        uint64_t c = first_chunk[i] + rec_chunk[j];
+        for (uint64_t done = 0; done < content; done += kManifestChunk, ++c) {
+            const uint32_t len = (uint32_t)min((uint64_t)kManifestChunk, content - done);
+            chunk_off[c] = rec + done;  // page convention: the chunk's content starts 8 bytes on
+            chunk_len[c] = len;
+            longs += len >= kLongMin ? 1 : 0;
+        }
+    }
+    // a count, the same whatever the order of the additions: k_mscan_long leaves at once when it is 0
+    longs = wave_sum(longs);
+    if ((threadIdx.x & 63) == 0 && longs) atomicAdd(n_long, (unsigned long long)longs);
+}
+
+__global__ __launch_bounds__(256) void k_mscan_hash(const uint8_t* __restrict__ base, const uint64_t* __restrict__ ctl,
+                                                   const uint64_t* __restrict__ chunk_off,
+                                                   const uint32_t* __restrict__ chunk_len,
+                                                   uint64_t* __restrict__ chunk_h) {
+    if (ctl[0] != ~0ull) return;
+    const uint64_t n_chunks = ctl[3];
+    const Xxh3Lane L = make_xxh3_lane(threadIdx.x & 15);
+    const uint64_t ntiles = (n_chunks + 15) / 16;
+    for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const uint64_t c = t * 16 + (threadIdx.x >> 4);
+        if (c >= n_chunks) continue;
+        const uint64_t o = chunk_off[c];
+        const uint32_t len = chunk_len[c];
+        if (len >= kLongMin) continue;  // k_mscan_long's
+        const uint8_t* page = base + o;
+        if (xxh3_group_ok(len + 8)) {
+            uint64_t stored;
+            const uint64_t h = xxh3_page_any<false>(page, len + 8, L, stored);
+            if (L.g == 0) chunk_h[c] = h;
+        } else if (L.g == 0) {
+            chunk_h[c] = xxh3_short(page + 8, len);
+        }
+    }
+}
+
+// The chunks of kLongMin bytes and more, a workgroup each (k_xxh3_long's body):
+// the 1 MiB chunks of snapshots and their long tails.  The content starts at
+// 8 mod 16, so the range is 8-byte aligned as that body needs.
+__global__ __launch_bounds__(256) void k_mscan_long(const uint8_t* __restrict__ base, const uint64_t* __restrict__ ctl,
+                                                   const uint64_t* __restrict__ chunk_off,
+                                                   const uint32_t* __restrict__ chunk_len,
+                                                   uint64_t* __restrict__ chunk_h) {
+    __shared__ uint64_t S[kLongWin][8];
+    if (ctl[0] != ~0ull || ctl[4] == 0) return;
+    const uint64_t n_chunks = ctl[3];
+    for (uint64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+        const uint32_t len = chunk_len[c];
+        if (len < kLongMin) continue;  // uniform over the workgroup
+        xxh3_long_range(S, base + chunk_off[c] + 8, len, chunk_h + c);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_mscan_report(const uint8_t* __restrict__ base, const uint64_t* __restrict__ off,
+                                                     const uint64_t* __restrict__ size, uint32_t shift,
+                                                     const uint64_t* __restrict__ slot_base,
+                                                     const uint64_t* __restrict__ ctl, const uint64_t* __restrict__ img,
+                                                     const uint64_t* __restrict__ first_rec,
+                                                     const uint64_t* __restrict__ first_chunk,
+                                                     const uint32_t* __restrict__ slot_len,
+                                                     const uint32_t* __restrict__ rec_slot,
+                                                     const uint32_t* __restrict__ rec_chunk,
+                                                     const uint64_t* __restrict__ chunk_h, uint64_t cap,
+                                                     uint64_t* __restrict__ records, uint64_t* __restrict__ reports) {
+    __shared__ unsigned long long red[3];  // ok records, first corrupt record, largest record
+    if (ctl[0] != ~0ull) return;
+    const uint64_t i = blockIdx.x;
+    if (threadIdx.x < 3) red[threadIdx.x] = threadIdx.x == 1 ? ~0ull : 0ull;
+    __syncthreads();
+    const uint64_t sb = slot_base[i], n_rec = img[4 * i], r0 = first_rec[i], c0 = first_chunk[i];
+    const uint8_t* image = base + off[i];
+    uint64_t n_ok = 0, first_bad = ~0ull, largest = 0;
+    for (uint64_t k = threadIdx.x; k < n_rec; k += 256) {
+        const uint32_t slot = rec_slot[sb + k];
+        const uint32_t len = slot_len[sb + slot];
+        const uint64_t o = (uint64_t)slot << shift;
+        const uint64_t content = 12ull + len;
+        const uint64_t* h = chunk_h + c0 + rec_chunk[sb + k];
+        uint64_t agg = 0;
+        for (uint64_t done = 0; done < content; done += kManifestChunk, ++h)
+            agg = (((agg << 1) | (agg >> 63)) ^ *h) * 0x9e3779b97f4a7c15ull;
+        const uint64_t* head = reinterpret_cast<const uint64_t*>(image + o);  // 8-byte aligned
+        const uint64_t stored = head[0], roots = head[1];
+        const bool ok = stored == agg;
+        if (ok) ++n_ok;
+        else if (first_bad == ~0ull) first_bad = k;  // a lane's records ascend
+        largest = max(largest, kMscanHeader + len);
+        if (r0 + k < cap) {
+            uint64_t* e = records + (r0 + k) * kMscanRecordWords;
+            e[0] = o;
+            e[1] = stored;
+            e[2] = agg;
+            e[3] = (uint64_t)len | (roots << 32);
+            e[4] = (roots >> 32) | ((uint64_t)(ok ? 1 : 0) << 32);
+        }
+    }
+    n_ok = wave_sum(n_ok);
+    first_bad = wave_min(first_bad);
+    largest = wave_max(largest);
+    if ((threadIdx.x & 63) == 0) {
+        if (n_ok) atomicAdd(&red[0], (unsigned long long)n_ok);
+        atomicMin(&red[1], (unsigned long long)first_bad);
+        atomicMax(&red[2], (unsigned long long)largest);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint64_t ok = red[0], fc = red[1];
+        const uint64_t after = fc == ~0ull ? 0 : ok - fc;  // every record before the first corrupt one is ok
+        const uint64_t end_off = img[4 * i + 2];
+        uint64_t* r = reports + i * kMscanReportWords;
+        r[0] = size[i];
+        r[1] = n_rec;
+        r[2] = ok;
+        r[3] = n_rec - ok;
+        r[4] = fc;
+        r[5] = after;
+        r[6] = fc == ~0ull ? end_off : (uint64_t)rec_slot[sb + fc] << shift;
+        r[7] = end_off;
+        r[8] = img[4 * i + 3];
+        r[9] = n_rec == 0 ? 4 : fc == 0 ? 3 : fc == ~0ull ? 0 : after ? 2 : 1;
+        r[10] = r0;
+        r[11] = red[2];
+    }
+}
+
+__global__ __launch_bounds__(256) void k_mscan_summary(uint64_t n_images, const uint64_t* __restrict__ ctl,
+                                                      const uint64_t* __restrict__ reports, uint64_t cap,
+                                                      uint64_t* __restrict__ summary) {
+    __shared__ unsigned long long tot[9];  // records, ok, corrupt, images by verdict 0..4, first bad image
+    const uint64_t invalid = ctl[0];
+    if (invalid != ~0ull) {  // uniform: only n_images and the invalid image are reported
+        if (threadIdx.x < kMscanSummaryWords) summary[threadIdx.x] = threadIdx.x == 0 ? n_images : threadIdx.x == 11 ? invalid : 0;
+        return;
+    }
+    if (threadIdx.x < 9) tot[threadIdx.x] = threadIdx.x == 8 ? ~0ull : 0ull;
+    __syncthreads();
+    uint64_t acc[8] = {};
+    uint64_t first_bad = ~0ull;
+    for (uint64_t i = threadIdx.x; i < n_images; i += 256) {
+        const uint64_t* r = reports + i * kMscanReportWords;
+        acc[0] += r[1];
+        acc[1] += r[2];
+        acc[2] += r[3];
+        const uint64_t v = r[9];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) acc[3 + k] += v == (uint64_t)k ? 1 : 0;
+        if (v != 0 && first_bad == ~0ull) first_bad = i;
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const uint64_t v = wave_sum(acc[k]);
+        if ((threadIdx.x & 63) == 0 && v) atomicAdd(&tot[k], (unsigned long long)v);
+    }
+    if (first_bad != ~0ull) atomicMin(&tot[8], (unsigned long long)first_bad);
+    __syncthreads();
+    if (threadIdx.x < kMscanSummaryWords) {
+        uint64_t v;
+        switch (threadIdx.x) {
+            case 0: v = n_images; break;
+            case 10: v = tot[0] < cap ? tot[0] : cap; break;
+            case 11: v = ~0ull; break;
+            default: v = tot[threadIdx.x - 1]; break;  // 1..9: records, ok, corrupt, verdicts, first bad image
+        }
+        summary[threadIdx.x] = v;
+    }
+}
+
+// Slots per LDS tile of k_mscan_walk (PCS_TUNE_MANIFEST_WALK_TILE): a power of
+// two in [64, kMscanMaxTile]; anything else runs at the default.
+constexpr uint32_t kMscanDefaultTile = 2048;
+uint32_t mscan_tile() {
+    const int64_t t = g_tune[38].load(std::memory_order_relaxed);
+    if (t < 64 || t > kMscanMaxTile || (t & (t - 1)) != 0) return kMscanDefaultTile;
+    return (uint32_t)t;
+}
+
+hipError_t run_manifest_scan(const uint8_t* base, uint64_t total, const uint64_t* off, const uint64_t* size,
+                             uint64_t n_images, uint32_t align, uint64_t* reports, uint64_t* summary,
+                             uint64_t* records, uint64_t cap, hipStream_t s) {
+    uint32_t shift = 0;
+    while ((1u << shift) < align) ++shift;
+    // the most slots and chunks a valid layout can give
+    const uint64_t max_slots = (total >> shift) + n_images;
+    const uint64_t max_chunks = max_slots + (total >> 20);
+    if (n_images > 0x7FFFFFFFull || max_chunks > 0x7FFFFFF0ull) return hipErrorInvalidValue;
+    ScratchLease scratch(s);
+    // u64: ctl, slot_base[n + 1], img[4 n], first_rec[n], first_chunk[n], chunk_off, chunk_h[max_chunks];
+    // u32: slot_next, slot_len, rec_slot, rec_chunk[max_slots], chunk_len[max_chunks]
+    const size_t words = kMscanCtlWords + (n_images + 1) + 6 * n_images + 2 * max_chunks;
+    hipError_t e = scratch.get(words * 8 + (4 * max_slots + max_chunks) * 4);
+    if (e != hipSuccess) return e;
+    uint64_t* ctl = static_cast<uint64_t*>(scratch.p);
+    uint64_t* slot_base = ctl + kMscanCtlWords;
+    uint64_t* img = slot_base + n_images + 1;
+    uint64_t* first_rec = img + 4 * n_images;
+    uint64_t* first_chunk = first_rec + n_images;
+    uint64_t* chunk_off = first_chunk + n_images;
+    uint64_t* chunk_h = chunk_off + max_chunks;
+    uint32_t* slot_next = reinterpret_cast<uint32_t*>(chunk_h + max_chunks);
+    uint32_t* slot_len = slot_next + max_slots;
+    uint32_t* rec_slot = slot_len + max_slots;
+    uint32_t* rec_chunk = rec_slot + max_slots;
+    uint32_t* chunk_len = rec_chunk + max_slots;
+    hipLaunchKernelGGL(k_mscan_layout, dim3(1), dim3(256), 0, s, off, size, n_images, total, shift, slot_base, ctl);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (n_images) {
+        const uint32_t tile = mscan_tile();
+        hipLaunchKernelGGL(k_mscan_slots, dim3(grid_for(max_slots, kBlock, kBlocksPerCu)), dim3(kBlock), 0, s, base, off,
+                           size, n_images, shift, slot_base, ctl, slot_next, slot_len);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_mscan_walk, dim3((unsigned)n_images), dim3(64), 3 * tile * sizeof(uint32_t), s, size,
+                           n_images, shift, tile, slot_base, ctl, slot_next, slot_len, rec_slot, rec_chunk, img);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_mscan_plan, dim3(1), dim3(256), 0, s, n_images, img, first_rec, first_chunk, ctl);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_mscan_emit, dim3(grid_for(max_chunks, kBlock, kBlocksPerCu)), dim3(kBlock), 0, s, off,
+                           n_images, shift, slot_base, ctl, img, first_chunk, slot_len, rec_slot, rec_chunk, chunk_off,
+                           chunk_len, reinterpret_cast<unsigned long long*>(ctl + 4));
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_mscan_hash, dim3(grid_for(max_chunks, 16, 32)), dim3(kBlock), 0, s, base, ctl, chunk_off,
+                           chunk_len, chunk_h);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_mscan_long, dim3(grid_for(max_chunks, 1, 8)), dim3(kBlock), 0, s, base, ctl, chunk_off,
+                           chunk_len, chunk_h);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_mscan_report, dim3((unsigned)n_images), dim3(256), 0, s, base, off, size, shift, slot_base,
+                           ctl, img, first_rec, first_chunk, slot_len, rec_slot, rec_chunk, chunk_h, cap, records,
+                           reports);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_mscan_summary, dim3(1), dim3(256), 0, s, n_images, ctl, reports, cap, summary);
     return hipGetLastError();
 }
 

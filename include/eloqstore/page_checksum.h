@@ -191,6 +191,46 @@ int TryScrubFiles(std::span<const char* const> pages, size_t page_size, uint64_t
 FilesReport ScrubFiles(std::span<const char* const> pages, size_t page_size, uint64_t pages_per_file,
                        size_t max_listed = 1024);
 
+// Manifest scan (pcs_manifest_scan_host): walks every record of many manifest
+// images in one call and checks each against ManifestBuilder::CalcChecksum,
+// following Replayer::ParseNextRecord (src/replayer.cpp:74-140).  Image i is
+// images[i], a whole manifest file in host memory (any alignment); align is
+// the record alignment (page_align).  A manifest's verdict maps to the
+// replayer's outcome: kClean replays whole, kTornTail is cut back to
+// valid_prefix_bytes, kBroken is KvError::Corrupted (replayer.cpp:60-63),
+// kBadSnapshot fails the open (replayer.cpp:37-38), kEmpty has no record.
+enum class ManifestVerdict : uint64_t { kClean = 0, kTornTail = 1, kBroken = 2, kBadSnapshot = 3, kEmpty = 4 };
+enum class ManifestEnd : uint64_t { kClean = 0, kShortHeader = 1, kShortPayload = 2, kShortPadding = 3 };
+struct ManifestRecord {
+    uint64_t offset = 0;                // in its image
+    uint64_t stored = 0, computed = 0;  // the record's checksum word / CalcChecksum of its content
+    uint32_t payload_len = 0, root = 0, ttl_root = 0, ok = 0;
+};
+struct ManifestReport {
+    uint64_t size = 0, n_records = 0, n_ok = 0, n_corrupt = 0;
+    uint64_t first_corrupt = UINT64_MAX;  // record index in the image
+    uint64_t n_ok_after_corrupt = 0;
+    uint64_t valid_prefix_bytes = 0;      // offset of the first corrupt record, else where the walk stopped
+    uint64_t end_offset = 0;
+    ManifestEnd end_reason = ManifestEnd::kClean;
+    ManifestVerdict verdict = ManifestVerdict::kEmpty;
+    uint64_t first_record = 0;            // index of the image's record 0 in ManifestsReport::records
+    uint64_t max_record_bytes = 0;
+};
+struct ManifestsReport {
+    std::vector<ManifestReport> manifests;
+    uint64_t n_records = 0, n_ok = 0, n_corrupt = 0;
+    uint64_t n_by_verdict[5] = {};
+    uint64_t first_bad_manifest = UINT64_MAX;  // first verdict other than kClean
+    std::vector<ManifestRecord> records;       // the first min(n_records, max_records) records, images in order
+};
+// PCS_OK or a negative pcs_status (message in LastChecksumError()); a failed
+// call leaves the report unspecified.
+int TryScanManifests(std::span<const std::string_view> images, ManifestsReport& report, uint32_t align = 4096,
+                     size_t max_records = 1 << 16);
+ManifestsReport ScanManifests(std::span<const std::string_view> images, uint32_t align = 4096,
+                              size_t max_records = 1 << 16);
+
 // Registers a page-pool chunk or io_uring buffer ring once (PagesPool::Extend,
 // src/storage/page.cpp:95-120): batches whose pages all lie in registered
 // memory are then hashed in place over PCIe in one launch, with no gather

@@ -102,7 +102,9 @@ enum pcs_flags {
  *      symbol): pcs_scrub_extents_dev / pcs_pages_scrub_extents_host, struct
  *      pcs_extent and struct pcs_extent_summary; pcs_scrub_files_dev /
  *      pcs_pages_scrub_files_host, struct pcs_file_report and struct
- *      pcs_files_summary */
+ *      pcs_files_summary; pcs_manifest_scan_dev / pcs_manifest_scan_host, struct
+ *      pcs_manifest_record, pcs_manifest_report and pcs_manifest_summary, and
+ *      PCS_TUNE_MANIFEST_WALK_TILE */
 #define PCS_ABI_VERSION 7
 int pcs_abi_version(void);
 const char *pcs_version(void);
@@ -475,6 +477,105 @@ int pcs_manifest_checksum_host(const void *content, uint64_t len, uint64_t *out)
  * the 20-byte header never validate. */
 int pcs_manifest_validate_host(const void *record, uint64_t size, int *valid);
 
+/* ---- manifest scan: walk and verify every record of many manifests ---------
+ * A store directory holds one manifest per partition: a snapshot record
+ * followed by appended log records, each checksum(8) | root(4) | ttl_root(4) |
+ * payload_len(4) | payload and padded to `align` (page_align, 4096).  The scan
+ * finds the records of every image of a batch and checks each, as
+ * Replayer::ParseNextRecord does one record at a time (src/replayer.cpp:74-140)
+ * and tools/manifest_check_tool.cpp does for one file.
+ *
+ * Walk rule, per image of `size` bytes, from offset o = 0:
+ *   o == size                -> stop, PCS_MANIFEST_END_CLEAN
+ *   size - o < 20            -> stop, PCS_MANIFEST_END_SHORT_HEADER
+ *   len = LE32 at o + 16, e = o + 20 + len in 64 bits (len may be any uint32_t)
+ *   e > size                 -> stop, PCS_MANIFEST_END_SHORT_PAYLOAD; the
+ *                               incomplete record is not a record
+ *   otherwise [o, e) is a record, ok iff the LE64 at o equals
+ *   ManifestBuilder::CalcChecksum of bytes [o + 8, e) (the 1 MiB chunks counted
+ *   from o + 8, pcs_manifest_checksum_dev's aggregate)
+ *   o' = e rounded up to align; o' > size -> stop, PCS_MANIFEST_END_SHORT_PADDING
+ *   with end_offset = size; otherwise o = o' and go on.
+ * end_offset is the offset at which the walk stopped.  The verdict follows
+ * from the ok flags alone.  A length is followed only after its bounds test,
+ * so no payload_len causes a read outside [d_base, d_base + total_bytes), and
+ * bytes inside a record's payload that look like a header are never a record.
+ *
+ * Layout (pcs_manifest_scan_dev): image i is [d_base + d_img_off[i], +
+ * d_img_size[i]); align is a power of two in [64, 65536]; d_base and d_records
+ * are 8-byte aligned; every offset is a multiple of align; the images ascend
+ * and are disjoint, d_img_off[i] >= roundup(d_img_off[i - 1] + d_img_size[i -
+ * 1], align); d_img_off[i] + d_img_size[i] <= total_bytes.  Offsets and sizes
+ * are DEVICE arrays which the host cannot see, so the kernels check them:
+ * invalid_image is the first i that breaks a rule, and when it is set every
+ * other summary word but n_images is 0 and no report or record is written.
+ * d_img_size[i] == 0 is legal: PCS_MANIFEST_EMPTY, END_CLEAN, first_corrupt
+ * UINT64_MAX.  total_bytes / align + n_images + total_bytes / 2^20 must stay
+ * below 2^31 (PCS_ERR_INVALID otherwise).
+ *
+ * d_records[first_record + k] is record k of the image, in walk order with the
+ * images in order, for every index below record_cap; entries at n_listed and
+ * beyond are not written; the counts are always full.  The output is the same
+ * from call to call (no atomic append).  d_records may be NULL iff record_cap
+ * == 0.  The _dev form enqueues on `stream` and never synchronises; its
+ * scratch is event-fenced per stream and sized from total_bytes, align and
+ * n_images alone.  Every call writes the whole summary, n_images == 0
+ * included.  The walk reads one aligned word per align-slot of every image,
+ * all independent, and follows the chain through those words in LDS, never
+ * through the image.
+ *
+ * pcs_manifest_scan_host is synchronous and takes host pointers throughout
+ * (plain or pinned, any alignment).  It checks its arguments on the host,
+ * copies the images into the calling thread's pinned staging at multiples of
+ * align, DMAs them and runs the _dev form; never zero-copy, never the service.
+ * Staging budget: 32 MiB of packed images per group; a batch above it goes
+ * through in groups of whole images (an image larger than the budget is a
+ * group of its own), and first_record and the summary are those of one call
+ * over the whole batch.  invalid_image is UINT64_MAX.  PCS_TUNE_FAIL_INJECT
+ * applies to it. */
+enum pcs_manifest_end {               /* why an image's walk stopped */
+    PCS_MANIFEST_END_CLEAN = 0,         /* next record offset == size */
+    PCS_MANIFEST_END_SHORT_HEADER = 1,  /* 0 < size - offset < 20 */
+    PCS_MANIFEST_END_SHORT_PAYLOAD = 2, /* offset + 20 + payload_len > size */
+    PCS_MANIFEST_END_SHORT_PADDING = 3, /* last record complete, its padding cut by the end of the image */
+};
+enum pcs_manifest_verdict {
+    PCS_MANIFEST_CLEAN = 0,        /* >= 1 record, every record ok */
+    PCS_MANIFEST_TORN_TAIL = 1,    /* record 0 ok; every record from the first corrupt one on is corrupt:
+                                      the replayer drops them and cuts the file back */
+    PCS_MANIFEST_BROKEN = 2,       /* record 0 ok; an ok record follows a corrupt one (replayer.cpp:60-63) */
+    PCS_MANIFEST_BAD_SNAPSHOT = 3, /* record 0 corrupt (replayer.cpp:37-38) */
+    PCS_MANIFEST_EMPTY = 4,        /* no complete record */
+};
+typedef struct pcs_manifest_record { /* 40 bytes, the same layout on device and host */
+    uint64_t offset;                 /* in its image; a multiple of align */
+    uint64_t stored, computed;       /* LE u64 at [0, 8) / CalcChecksum(record[8 .. 20 + payload_len)) */
+    uint32_t payload_len, root, ttl_root, ok;
+} pcs_manifest_record;
+typedef struct pcs_manifest_report { /* 12 x u64, one per image */
+    uint64_t size, n_records, n_ok, n_corrupt;
+    uint64_t first_corrupt;          /* record index in the image, UINT64_MAX when none */
+    uint64_t n_ok_after_corrupt;     /* ok records after the first corrupt one */
+    uint64_t valid_prefix_bytes;     /* offset of the first corrupt record, else the offset where the walk stopped */
+    uint64_t end_offset, end_reason, verdict;
+    uint64_t first_record;           /* index of the image's record 0 in d_records (exclusive sum of n_records) */
+    uint64_t max_record_bytes;       /* largest 20 + payload_len walked, 0 when none */
+} pcs_manifest_report;
+typedef struct pcs_manifest_summary { /* 12 x u64 */
+    uint64_t n_images, n_records, n_ok, n_corrupt;
+    uint64_t n_by_verdict[5];
+    uint64_t first_bad_image;        /* first image whose verdict is not CLEAN, UINT64_MAX when none */
+    uint64_t n_listed;               /* min(n_records, record_cap) */
+    uint64_t invalid_image;          /* UINT64_MAX when the layout is valid */
+} pcs_manifest_summary;
+int pcs_manifest_scan_dev(const void *d_base, uint64_t total_bytes, const uint64_t *d_img_off,
+                          const uint64_t *d_img_size, uint64_t n_images, uint32_t align,
+                          pcs_manifest_report *d_reports, pcs_manifest_summary *d_summary,
+                          pcs_manifest_record *d_records, uint64_t record_cap, pcs_stream_t stream);
+int pcs_manifest_scan_host(const void *const *images, const uint64_t *sizes, uint64_t n_images,
+                           uint32_t align, pcs_manifest_report *reports, pcs_manifest_summary *summary,
+                           pcs_manifest_record *records, uint64_t record_cap);
+
 /* ---- sharding ------------------------------------------------------------
  * Contiguous page range [begin, end) of rank `rank` of `world` for n pages:
  * begin = floor(rank * n / world).  Pages are independent, so G GPUs hash G
@@ -581,6 +682,10 @@ int pcs_shard_range(uint64_t n, int world, int rank, uint64_t *begin, uint64_t *
  *                                     and asks the runtime about the kernel
  *                                     every 1 ms; 0: asks the runtime every
  *                                     50 µs (round 6 before this key)
+ *   PCS_TUNE_MANIFEST_WALK_TILE [2048] manifest scan: align-slots per LDS tile
+ *                                     of the chain walk, a power of two in
+ *                                     [64, 4096] (any other value runs at the
+ *                                     default); results do not depend on it
  * Keys 4, 5, 10, 12, 14, 16-22, 25, 29 and 32 selected variants that measured slower or no
  * better (XXH64 quad nt loads, in-place stamp widths, descriptor tile sorts,
  * 4 KiB slices, wave-dealt pages and slice streams, pipelined split-page
@@ -612,6 +717,7 @@ enum pcs_tune_key {
     PCS_TUNE_ZC_BATCH_EVENT = 34,
     PCS_TUNE_SYNC_SPIN_US = 35,
     PCS_TUNE_SERVICE_DEPARTURE = 36,
+    PCS_TUNE_MANIFEST_WALK_TILE = 38, /* 37 was never assigned and stays unknown */
 };
 int pcs_set_tuning(int key, int64_t value);
 int64_t pcs_get_tuning(int key); /* -1 for an unknown key */

@@ -35,6 +35,19 @@
 //       line per file that has a corrupted page or a hole, then the totals.
 //       Exit 2 if any file has a corrupted page, else 3 if any has a hole,
 //       else 0.  A file with no whole page is skipped with a warning.
+//   page_checksum_tool --check-manifest <file>...   walk and verify every record
+//       of manifest files (the reference's tools/manifest_check_tool.cpp, whose
+//       one-file contract is kept): all files of the invocation go through one
+//       pcs_manifest_scan_host call at page_align 4096.  One file: that tool's
+//       output ("Log #i at offset ...", record size, root, ttl_root,
+//       payload_bytes, checksum: OK|FAILED, payload_hex for failed records,
+//       "Parsed N logs from <path>") and exit codes: 0, 2 on any checksum
+//       failure, 1 with its messages for a truncated header or payload or for
+//       no records; padding cut by the end of the file is no error, as there.
+//       Several files: one line per file (records, corrupt, verdict,
+//       valid_prefix_bytes); exit 2 if any manifest is broken or has a bad
+//       snapshot, else 3 if any has a torn tail, else 1 if any is empty or
+//       unreadable, else 0.
 //   --scan/--stamp print a summary line with the GiB/s of the call; exit codes
 //   as above (--scan: 2 if any page is corrupted).
 #include <fcntl.h>
@@ -56,6 +69,7 @@
 #include "eloqstore_pcs.h"
 #include "extent_merge.h"
 #include "file_merge.h"
+#include "manifest_scan.h"
 #include "scrub_merge.h"
 
 namespace {
@@ -83,8 +97,11 @@ void usage(const char* prog) {
                  "           exit 2: corrupted pages; exit 3: a blank page below the last written one\n"
                  "           (a lost write only for append-mode files, which are written in page order)\n"
                  "       %s --scrub-files <page_size_bytes> <file>...\n"
-                 "       %s --gen <file_path> <n_pages> [page_size_bytes] [seed]\n",
-                 prog, prog, prog, prog, prog, prog);
+                 "       %s --gen <file_path> <n_pages> [page_size_bytes] [seed]\n"
+                 "       %s --check-manifest <manifest_file>...\n"
+                 "           one file: the manifest_check_tool report (exit 2: a checksum failed);\n"
+                 "           several: a line per file (exit 2: broken or bad snapshot, 3: torn tail, 1: empty)\n",
+                 prog, prog, prog, prog, prog, prog, prog);
 }
 
 constexpr uint64_t kDefaultPageSize = 4096;  // KvOptions{}.data_page_size
@@ -622,7 +639,66 @@ int gen(const char* path, const char* n_s, const char* size_s, const char* seed_
 
 }  // namespace
 
+// --check-manifest: every file is read whole into memory and all of them go
+// through one pcs_manifest_scan_host call; an unreadable file is reported and
+// left out of the call.
+int check_manifests(int n_paths, char** paths) {
+    constexpr uint32_t kPageAlign = 4096;  // page_align, include/storage/page.h
+    std::vector<std::vector<char>> data;
+    std::vector<const char*> names;
+    bool unreadable = false;
+    for (int i = 0; i < n_paths; ++i) {
+        FILE* f = std::fopen(paths[i], "rb");
+        if (!f) {
+            std::fprintf(stderr, "Failed to open %s: %s\n", paths[i], std::strerror(errno));
+            if (n_paths == 1) return 1;
+            unreadable = true;
+            continue;
+        }
+        std::vector<char> bytes;
+        char chunk[1 << 16];
+        size_t got;
+        while ((got = std::fread(chunk, 1, sizeof chunk, f)) > 0) bytes.insert(bytes.end(), chunk, chunk + got);
+        std::fclose(f);
+        data.push_back(std::move(bytes));
+        names.push_back(paths[i]);
+    }
+    const uint64_t n = data.size();
+    std::vector<const void*> ptrs(n);
+    std::vector<uint64_t> sizes(n);
+    uint64_t cap = 0;  // a record per 4 KiB slot at most
+    for (uint64_t i = 0; i < n; ++i) {
+        ptrs[i] = data[i].data();
+        sizes[i] = data[i].size();
+        cap += sizes[i] / kPageAlign + 1;
+    }
+    std::vector<pcs_manifest_report> reports(n);
+    std::vector<pcs_manifest_record> records(n_paths == 1 ? cap : 0);
+    pcs_manifest_summary sum{};
+    if (const int rc = pcs_manifest_scan_host(ptrs.data(), sizes.data(), n, kPageAlign, reports.data(), &sum,
+                                              records.data(), records.size())) {
+        std::fprintf(stderr, "Manifest scan failed (%d): %s\n", rc, pcs_last_error());
+        return 1;
+    }
+    if (n_paths == 1) {
+        const pcs::ManifestToolText t = pcs::manifest_tool_text(
+            names[0], reinterpret_cast<const uint8_t*>(data[0].data()), reports[0], records.data());
+        std::fputs(t.out.c_str(), stdout);
+        std::fputs(t.err.c_str(), stderr);
+        return t.exit_code;
+    }
+    for (uint64_t i = 0; i < n; ++i) std::fputs(pcs::manifest_tool_line(names[i], reports[i]).c_str(), stdout);
+    return pcs::manifest_tool_exit(reports.data(), n, unreadable);
+}
+
 int main(int argc, char** argv) {
+    if (argc >= 2 && !std::strcmp(argv[1], "--check-manifest")) {
+        if (argc < 3) {
+            usage(argv[0]);
+            return 1;
+        }
+        return check_manifests(argc - 2, argv + 2);
+    }
     if (argc >= 2 && (!std::strcmp(argv[1], "--scan") || !std::strcmp(argv[1], "--stamp"))) {
         if (argc < 3 || argc > 4) {
             usage(argv[0]);
