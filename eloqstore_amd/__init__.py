@@ -83,6 +83,10 @@ _SIGS = {
     "pcs_manifest_validate_host": [_vp, _u64, _P(_i32)],
     "pcs_manifest_scan_dev": [_vp, _u64, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _u64, _vp],
     "pcs_manifest_scan_host": [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _u64],
+    "pcs_manifest_replay_dev": [_vp, _u64, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp, _u64, _vp],
+    "pcs_manifest_replay_host": [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp, _u64],
+    "pcs_scrub_live_dev": [_vp, _u64, _u64, _vp, _u64, _vp, _vp, _vp, _u64, _vp],
+    "pcs_scrub_live_host": [_vp, _u64, _u64, _vp, _u64, _vp, _vp, _vp, _u64],
     "pcs_set_tuning": [_i32, ctypes.c_int64],
     "pcs_get_tuning": [_i32],
     "pcs_counter": [_i32],
@@ -180,6 +184,7 @@ TUNE_ZC_BATCH_EVENT = 34
 TUNE_SYNC_SPIN_US = 35
 TUNE_SERVICE_DEPARTURE = 36
 TUNE_MANIFEST_WALK_TILE = 38
+TUNE_REPLAY_TILE = 39
 
 # PCS_PATH_* bits (pcs_last_path / pcs_batch_path)
 PATH_SERVED = 1
@@ -555,6 +560,154 @@ def manifest_scan_host(images: list, align: int = 4096, record_cap: int = 1024):
     _call("pcs_manifest_scan_host", ptrs.ctypes.data, sizes.ctypes.data, n, align, reports.ctypes.data,
           summary.ctypes.data, records.ctypes.data if record_cap else 0, record_cap)
     return reports[:n], summary[0], records[: int(summary[0]["n_listed"])]
+
+
+# pcs_replay_report (16 u64 words), pcs_replay_summary (12), pcs_live_page (16 bytes), pcs_live_summary (16)
+REPLAY_REPORT_DTYPE = np.dtype([(k, "<u8") for k in (
+    "status", "n_replayed", "malformed_record", "root", "ttl_root", "max_fp_id", "dict_bytes", "snapshot_pages",
+    "n_log_entries", "table_size", "table_first", "n_mapped", "min_fp", "max_fp", "n_fp_beyond_max", "n_term_pairs")])
+REPLAY_SUMMARY_DTYPE = np.dtype([("n_images", "<u8"), ("n_by_status", "<u8", (4,)), ("n_rows", "<u8"),
+                                 ("n_rows_written", "<u8"), ("n_mapped", "<u8"), ("n_log_entries", "<u8"),
+                                 ("first_bad_image", "<u8"), ("invalid_image", "<u8"), ("reserved", "<u8")])
+LIVE_PAGE_DTYPE = np.dtype([("index", "<u8"), ("page_id", "<u4"), ("cls", "<u4")])
+LIVE_SUMMARY_DTYPE = np.dtype([(k, "<u8") for k in (
+    "n_pages", "table_size", "n_mapped", "n_mapped_in_window", "n_duplicate", "live_ok", "live_blank",
+    "live_corrupt", "dead_ok", "dead_blank", "dead_corrupt", "n_damaged", "first_damaged", "last_live", "n_listed",
+    "reserved")])
+REPLAY_OK, REPLAY_NOT_REPLAYABLE, REPLAY_MALFORMED, REPLAY_TABLE_CAP = range(4)
+REPLAY_STATUS = ("ok", "not_replayable", "malformed", "table_cap")
+MAPPING_INVALID = 7  # MappingSnapshot::InvalidValue: a table row nobody wrote
+NO_OWNER = 0xFFFFFFFF
+
+
+def manifest_replay_async(base, img_off, img_size, align: int = 4096, table_cap: int = 0, total_bytes: int | None = None,
+                          n_images: int | None = None, scan_reports=None, reports=None, summary=None, table=None,
+                          stream=None):
+    """pcs_manifest_replay_dev, enqueue only: base, img_off and img_size as for
+    manifest_scan_async; returns the device tensors (scan reports n x 12 int64
+    words, or None when scan_reports is False; reports n x 16; the 12 summary
+    words; the table of table_cap int64 rows, None when table_cap is 0), valid
+    once the stream is synchronised."""
+    if total_bytes is None:
+        total_bytes = base.numel()
+    if n_images is None:
+        n_images = img_off.numel()
+    if scan_reports is None:
+        scan_reports = torch.empty((max(n_images, 1), 12), dtype=torch.int64, device=base.device)
+    if reports is None:
+        reports = torch.empty((max(n_images, 1), 16), dtype=torch.int64, device=base.device)
+    if summary is None:
+        summary = torch.empty(12, dtype=torch.int64, device=base.device)
+    if table is None and table_cap:
+        table = torch.empty(table_cap, dtype=torch.int64, device=base.device)
+    _call("pcs_manifest_replay_dev", _ptr(base), total_bytes, _ptr(img_off), _ptr(img_size), n_images, align,
+          _ptr(None if scan_reports is False else scan_reports), _ptr(reports), _ptr(summary),
+          _ptr(table) if table_cap else 0, table_cap, _stream(stream))
+    return (None if scan_reports is False else scan_reports), reports, summary, (table if table_cap else None)
+
+
+def manifest_replay_dev(base, img_off, img_size, align: int = 4096, table_cap: int = 0, total_bytes: int | None = None,
+                        stream=None):
+    """Replay the manifest images held in the device tensor base -> (reports
+    (REPLAY_REPORT_DTYPE, one per image), summary (one REPLAY_SUMMARY_DTYPE
+    record), the n_rows_written table rows (uint64), scan reports
+    (MANIFEST_REPORT_DTYPE)).  Image i's rows are table[table_first :
+    table_first + table_size] when its status is REPLAY_OK.  Waits for the
+    stream.  With an invalid layout everything but the summary is empty."""
+    def dev(x):
+        if isinstance(x, torch.Tensor):
+            return x
+        return torch.from_numpy(np.ascontiguousarray(x, dtype=np.uint64).view(np.int64)).to(base.device)
+    img_off, img_size = dev(img_off), dev(img_size)
+    n = img_off.numel()
+    scan_reports, reports, summary, table = manifest_replay_async(base, img_off, img_size, align, table_cap,
+                                                                  total_bytes, n, stream=stream)
+    if stream is not None:  # the copies below are ordered on torch's current stream only
+        _call("pcs_synchronize", _stream(stream))
+    s = np.ascontiguousarray(summary.cpu().numpy()).view(np.uint64).view(REPLAY_SUMMARY_DTYPE)[0]
+    if int(s["invalid_image"]) != NO_PAGE:
+        return (np.zeros(0, dtype=REPLAY_REPORT_DTYPE), s, np.zeros(0, dtype=np.uint64),
+                np.zeros(0, dtype=MANIFEST_REPORT_DTYPE))
+    reps = np.ascontiguousarray(reports[:n].cpu().numpy()).view(np.uint64).view(REPLAY_REPORT_DTYPE).reshape(-1)
+    sreps = np.ascontiguousarray(scan_reports[:n].cpu().numpy()).view(np.uint64).view(MANIFEST_REPORT_DTYPE).reshape(-1)
+    rows = int(s["n_rows_written"])
+    tab = (np.ascontiguousarray(table[:rows].cpu().numpy()).view(np.uint64) if rows else np.zeros(0, dtype=np.uint64))
+    return reps, s, tab, sreps
+
+
+def manifest_replay_host(images: list, align: int = 4096, table_cap: int = 0):
+    """pcs_manifest_replay_host over whole manifest images in host memory ->
+    (reports, summary, table rows, scan reports) as manifest_replay_dev."""
+    n = len(images)
+    views = [np.frombuffer(b, dtype=np.uint8) if not isinstance(b, np.ndarray) else b for b in images]
+    ptrs = np.array([v.ctypes.data if v.size else 0 for v in views], dtype=np.uint64)
+    sizes = np.array([v.size for v in views], dtype=np.uint64)
+    scan_reports = np.zeros(max(1, n), dtype=MANIFEST_REPORT_DTYPE)
+    reports = np.zeros(max(1, n), dtype=REPLAY_REPORT_DTYPE)
+    summary = np.zeros(1, dtype=REPLAY_SUMMARY_DTYPE)
+    table = np.zeros(max(1, table_cap), dtype=np.uint64)
+    _call("pcs_manifest_replay_host", ptrs.ctypes.data, sizes.ctypes.data, n, align, scan_reports.ctypes.data,
+          reports.ctypes.data, summary.ctypes.data, table.ctypes.data if table_cap else 0, table_cap)
+    return reports[:n], summary[0], table[: int(summary[0]["n_rows_written"])], scan_reports[:n]
+
+
+def scrub_live_async(cls, n_pages: int, fp_first: int, table, table_size: int | None = None, owner=None,
+                     summary=None, damaged=None, damaged_cap: int = 1024, stream=None):
+    """pcs_scrub_live_dev, enqueue only: cls is a scrub's device class bytes
+    for file pages fp_first .. fp_first + n_pages, table a device int64 mapping
+    table (None with table_size 0); returns the device tensors (owner uint32 as
+    int32 words, or None when owner is False; the 16 summary words; the damaged
+    list as damaged_cap x 2 int64 words), valid once the stream is synchronised."""
+    device = cls.device
+    if table_size is None:
+        table_size = 0 if table is None else table.numel()
+    if owner is None:
+        owner = torch.empty(max(n_pages, 1), dtype=torch.int32, device=device)
+    if summary is None:
+        summary = torch.empty(16, dtype=torch.int64, device=device)
+    if damaged is None and damaged_cap:
+        damaged = torch.empty((damaged_cap, 2), dtype=torch.int64, device=device)
+    _call("pcs_scrub_live_dev", _ptr(cls), n_pages, fp_first, _ptr(table) if table_size else 0, table_size,
+          _ptr(None if owner is False else owner), _ptr(summary), _ptr(damaged) if damaged_cap else 0, damaged_cap,
+          _stream(stream))
+    return (None if owner is False else owner), summary, damaged
+
+
+def scrub_live(cls, n_pages: int, fp_first: int, table, table_size: int | None = None, owner=None,
+               damaged_cap: int = 1024, stream=None):
+    """Which pages of a scrubbed window a replayed table still points to ->
+    (owner (uint32 numpy array, NO_OWNER for dead pages; None when owner is
+    False), summary (one LIVE_SUMMARY_DTYPE record), the n_listed damaged live
+    pages (LIVE_PAGE_DTYPE)).  cls and table may be device tensors or host
+    arrays.  Waits for the stream."""
+    if not isinstance(cls, torch.Tensor):
+        cls = torch.from_numpy(np.ascontiguousarray(cls, dtype=np.uint8)).cuda()
+    if table is not None and not isinstance(table, torch.Tensor):
+        table = torch.from_numpy(np.ascontiguousarray(table, dtype=np.uint64).view(np.int64)).to(cls.device)
+    owner, summary, damaged = scrub_live_async(cls, n_pages, fp_first, table, table_size, owner, None, None,
+                                               damaged_cap, stream)
+    if stream is not None:
+        _call("pcs_synchronize", _stream(stream))
+    s = np.ascontiguousarray(summary.cpu().numpy()).view(np.uint64).view(LIVE_SUMMARY_DTYPE)[0]
+    listed = int(s["n_listed"])
+    pages = (np.ascontiguousarray(damaged[:listed].cpu().numpy()).view(np.uint8).view(LIVE_PAGE_DTYPE).reshape(-1)
+             if listed else np.zeros(0, dtype=LIVE_PAGE_DTYPE))
+    own = None if owner is None else np.ascontiguousarray(owner[:n_pages].cpu().numpy()).view(np.uint32)
+    return own, s, pages
+
+
+def scrub_live_host(cls, fp_first: int, table, damaged_cap: int = 1024, want_owner: bool = True):
+    """pcs_scrub_live_host over host arrays -> (owner, summary, damaged) as scrub_live."""
+    cls = np.ascontiguousarray(cls, dtype=np.uint8)
+    table = np.ascontiguousarray(table, dtype=np.uint64)
+    n = cls.size
+    owner = np.zeros(max(1, n), dtype=np.uint32)
+    summary = np.zeros(1, dtype=LIVE_SUMMARY_DTYPE)
+    damaged = np.zeros(max(1, damaged_cap), dtype=LIVE_PAGE_DTYPE)
+    _call("pcs_scrub_live_host", cls.ctypes.data if n else 0, n, fp_first, table.ctypes.data if table.size else 0,
+          table.size, owner.ctypes.data if want_owner else 0, summary.ctypes.data,
+          damaged.ctypes.data if damaged_cap else 0, damaged_cap)
+    return (owner[:n] if want_owner else None), summary[0], damaged[: int(summary[0]["n_listed"])]
 
 
 class Batch:

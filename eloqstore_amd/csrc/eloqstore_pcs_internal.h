@@ -78,6 +78,26 @@ hipError_t run_manifest(const uint8_t* content, uint64_t len, uint64_t* out, hip
 hipError_t run_manifest_scan(const uint8_t* base, uint64_t total, const uint64_t* off, const uint64_t* size,
                              uint64_t n_images, uint32_t align, uint64_t* reports, uint64_t* summary,
                              uint64_t* records, uint64_t cap, hipStream_t s);
+// Manifest replay over the same layout (total < 2^32): runs the scan with a
+// record array of its own bound in scratch, then decodes and applies the
+// mapping sections.  scan_reports (12 words per image) may be null; reports =
+// 16 words per image (pcs_replay_report), summary = the 12 words of
+// pcs_replay_summary.  Rows go to table[table_first + page_id] with
+// table_first counted from table_base (the rows of earlier groups of a host
+// batch; 0 for a whole batch) and tested against table_cap, both absolute row
+// indices of `table`.  All device memory; enqueues on s and never waits.
+hipError_t run_manifest_replay(const uint8_t* base, uint64_t total, const uint64_t* off, const uint64_t* size,
+                               uint64_t n_images, uint32_t align, uint64_t* scan_reports, uint64_t* reports,
+                               uint64_t* summary, uint64_t* table, uint64_t table_base, uint64_t table_cap,
+                               hipStream_t s);
+// Liveness of the file pages [fp_first, fp_first + n) whose class bytes are
+// cls[0 .. n), against the mapping table table[0 .. rows) (rows < 2^32):
+// owner[i] = the lowest row that maps page i, else UINT32_MAX (owner may be
+// null: scratch is leased), summary = the 16 words of pcs_live_summary,
+// list[0 .. min(n_damaged, cap)) = the damaged live pages as pcs_live_page,
+// ascending.  All device memory; enqueues on s and never waits.
+hipError_t run_scrub_live(const uint8_t* cls, uint64_t n, uint64_t fp_first, const uint64_t* table, uint64_t rows,
+                          uint32_t* owner, uint64_t* summary, uint64_t* list, uint64_t cap, hipStream_t s);
 // Event-fenced device scratch (see ScratchPool in pcs_kernels.hip): the
 // buffer is reused only after the work queued on `s` at release completes.
 hipError_t scratch_acquire(size_t bytes, void** out, int* id);

@@ -239,6 +239,112 @@ ManifestsReport ScanManifests(std::span<const std::string_view> images, uint32_t
     return report;
 }
 
+static ManifestReport to_report(const pcs_manifest_report& r) {
+    ManifestReport o;
+    o.size = r.size;
+    o.n_records = r.n_records;
+    o.n_ok = r.n_ok;
+    o.n_corrupt = r.n_corrupt;
+    o.first_corrupt = r.first_corrupt;
+    o.n_ok_after_corrupt = r.n_ok_after_corrupt;
+    o.valid_prefix_bytes = r.valid_prefix_bytes;
+    o.end_offset = r.end_offset;
+    o.end_reason = static_cast<ManifestEnd>(r.end_reason);
+    o.verdict = static_cast<ManifestVerdict>(r.verdict);
+    o.first_record = r.first_record;
+    o.max_record_bytes = r.max_record_bytes;
+    return o;
+}
+
+int TryReplayManifests(std::span<const std::string_view> images, ManifestsReplay& report, uint32_t align,
+                       size_t max_rows) {
+    const size_t n = images.size();
+    std::vector<const void*> ptrs(n);
+    std::vector<uint64_t> sizes(n);
+    for (size_t i = 0; i < n; ++i) {
+        ptrs[i] = images[i].data();
+        sizes[i] = images[i].size();
+    }
+    std::vector<pcs_manifest_report> scans(n);
+    std::vector<pcs_replay_report> reports(n);
+    pcs_replay_summary sum{};
+    report.table.resize(max_rows);
+    const int rc = pcs_manifest_replay_host(ptrs.data(), sizes.data(), n, align, scans.data(), reports.data(), &sum,
+                                            report.table.data(), max_rows);
+    if (rc != PCS_OK) return rc;
+    report.manifests.resize(n);
+    report.scans.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+        const pcs_replay_report& r = reports[i];
+        ManifestReplay& o = report.manifests[i];
+        o.status = static_cast<ReplayStatus>(r.status);
+        o.n_replayed = r.n_replayed;
+        o.malformed_record = r.malformed_record;
+        o.root = r.root;
+        o.ttl_root = r.ttl_root;
+        o.max_fp_id = r.max_fp_id;
+        o.dict_bytes = r.dict_bytes;
+        o.snapshot_pages = r.snapshot_pages;
+        o.n_log_entries = r.n_log_entries;
+        o.table_size = r.table_size;
+        o.table_first = r.table_first;
+        o.n_mapped = r.n_mapped;
+        o.min_fp = r.min_fp;
+        o.max_fp = r.max_fp;
+        o.n_fp_beyond_max = r.n_fp_beyond_max;
+        o.n_term_pairs = r.n_term_pairs;
+        report.scans[i] = to_report(scans[i]);
+    }
+    for (int k = 0; k < 4; ++k) report.n_by_status[k] = sum.n_by_status[k];
+    report.n_rows = sum.n_rows;
+    report.n_mapped = sum.n_mapped;
+    report.n_log_entries = sum.n_log_entries;
+    report.first_bad_manifest = sum.first_bad_image;
+    report.table.resize(sum.n_rows_written);
+    return PCS_OK;
+}
+
+ManifestsReplay ReplayManifests(std::span<const std::string_view> images, uint32_t align, size_t max_rows) {
+    ManifestsReplay report;
+    if (int rc = TryReplayManifests(images, report, align, max_rows)) die("ReplayManifests", rc);
+    return report;
+}
+
+int TryScrubLive(std::span<const uint8_t> classes, uint64_t fp_first, std::span<const uint64_t> table,
+                 LiveReport& report, size_t max_listed) {
+    static_assert(sizeof(LivePage) == sizeof(pcs_live_page), "LivePage mirrors pcs_live_page");
+    std::vector<pcs_live_page> listed(max_listed);
+    pcs_live_summary sum{};
+    report.owner.resize(classes.size());
+    const int rc = pcs_scrub_live_host(classes.data(), classes.size(), fp_first, table.data(), table.size(),
+                                       report.owner.data(), &sum, listed.data(), max_listed);
+    if (rc != PCS_OK) return rc;
+    report.n_pages = sum.n_pages;
+    report.table_size = sum.table_size;
+    report.n_mapped = sum.n_mapped;
+    report.n_mapped_in_window = sum.n_mapped_in_window;
+    report.n_duplicate = sum.n_duplicate;
+    report.live_ok = sum.live_ok;
+    report.live_blank = sum.live_blank;
+    report.live_corrupt = sum.live_corrupt;
+    report.dead_ok = sum.dead_ok;
+    report.dead_blank = sum.dead_blank;
+    report.dead_corrupt = sum.dead_corrupt;
+    report.n_damaged = sum.n_damaged;
+    report.first_damaged = sum.first_damaged;
+    report.last_live = sum.last_live;
+    report.damaged.resize(sum.n_listed);
+    for (size_t k = 0; k < sum.n_listed; ++k) report.damaged[k] = LivePage{listed[k].index, listed[k].page_id, listed[k].cls};
+    return PCS_OK;
+}
+
+LiveReport ScrubLive(std::span<const uint8_t> classes, uint64_t fp_first, std::span<const uint64_t> table,
+                     size_t max_listed) {
+    LiveReport report;
+    if (int rc = TryScrubLive(classes, fp_first, table, report, max_listed)) die("ScrubLive", rc);
+    return report;
+}
+
 void RegisterPagePool(void* base, size_t bytes) {
     if (int rc = pcs_host_register(base, bytes)) die("RegisterPagePool", rc);
 }

@@ -9,6 +9,7 @@
 #include "region_registry.h"
 #include "extent_merge.h"
 #include "file_merge.h"
+#include "manifest_replay.h"
 #include "manifest_scan.h"
 #include "scrub_merge.h"
 
@@ -1540,6 +1541,128 @@ int host_manifest_scan(const void* const* images, const uint64_t* sizes, uint64_
     return PCS_OK;
 }
 
+// pcs_manifest_replay_host: the scan's staging groups again, each replayed by
+// the device form into one device table of table_cap rows, counted from the
+// rows of the groups before it (ReplayCarry), so that table_first and the
+// TABLE_CAP rule are those of one call over the batch.  Reports come back per
+// group, the rows once at the end.  The device table (8 bytes per row of
+// table_cap) is held for the whole call; every group's device call leases its
+// sequence words (4 bytes per row) for the absolute cap again, from the pool,
+// so a batch of several groups reuses one buffer.
+int host_manifest_replay(const void* const* images, const uint64_t* sizes, uint64_t n_images, uint32_t align,
+                         pcs_manifest_report* scan_reports, pcs_replay_report* reports, pcs_replay_summary* summary,
+                         uint64_t* table, uint64_t table_cap) {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return hip_fail(e, "hipGetDevice");
+    Slot& slot = t_ctx[dev].slot[0];  // the calling thread's stream and staging on this device
+    void* tbuf = nullptr;
+    int tid = -1;
+    if (table_cap && (e = pcs::scratch_acquire(table_cap * 8, &tbuf, &tid)) != hipSuccess)
+        return finish(e, "manifest replay table");
+    uint64_t* d_table = static_cast<uint64_t*>(tbuf);
+    pcs::ReplayCarry carry;
+    hipStream_t s = nullptr;
+    for (const pcs::ManifestGroup& g : pcs::manifest_pack(sizes, n_images, align)) {
+        int rc = PCS_OK;
+        if (g.bytes >= (1ull << 32) || !pcs::manifest_batch_fits(g.bytes, g.count, align))
+            rc = fail(PCS_ERR_INVALID, "a group of images is too large");
+        if (!rc) rc = ensure_slot(slot, std::max<uint64_t>(g.bytes, 1), 1);
+        if (rc) {
+            if (tid >= 0) (void)pcs::scratch_release(tid, slot.stream);
+            return rc;
+        }
+        s = slot.stream;
+        for (uint64_t k = 0; k < g.count; ++k)
+            if (sizes[g.first + k]) std::memcpy(slot.h_pages + g.off[k], images[g.first + k], sizes[g.first + k]);
+        void* buf = nullptr;
+        int id = -1;
+        e = pcs::scratch_acquire(g.count * (16 + sizeof(pcs_manifest_report) + sizeof(pcs_replay_report)) +
+                                     sizeof(pcs_replay_summary),
+                                 &buf, &id);
+        uint64_t* d_off = static_cast<uint64_t*>(buf);
+        uint64_t* d_size = d_off + g.count;
+        pcs_manifest_report* d_srep = reinterpret_cast<pcs_manifest_report*>(d_size + g.count);
+        pcs_replay_report* d_rep = reinterpret_cast<pcs_replay_report*>(d_srep + g.count);
+        pcs_replay_summary* d_sum = reinterpret_cast<pcs_replay_summary*>(d_rep + g.count);
+        pcs_replay_summary sum{};
+        if (e == hipSuccess && g.bytes) e = hipMemcpyAsync(slot.d_pages, slot.h_pages, g.bytes, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_off, g.off.data(), g.count * 8, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_size, sizes + g.first, g.count * 8, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess)
+            e = pcs::run_manifest_replay(slot.d_pages, g.bytes, d_off, d_size, g.count, align,
+                                         reinterpret_cast<uint64_t*>(d_srep), reinterpret_cast<uint64_t*>(d_rep),
+                                         reinterpret_cast<uint64_t*>(d_sum), d_table, carry.rows, table_cap, s);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(reports + g.first, d_rep, g.count * sizeof(pcs_replay_report), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && scan_reports)
+            e = hipMemcpyAsync(scan_reports + g.first, d_srep, g.count * sizeof(pcs_manifest_report),
+                               hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(&sum, d_sum, sizeof(sum), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e == hipSuccess && sum.invalid_image != UINT64_MAX) e = hipErrorUnknown;  // the plan's own layout
+        if (id >= 0) (void)pcs::scratch_release(id, s);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(s);  // nothing of this call left in flight
+            if (tid >= 0) (void)pcs::scratch_release(tid, s);
+            return finish(e, "manifest replay");
+        }
+        carry.add(reports + g.first, g.count);
+    }
+    pcs::replay_summarize(reports, n_images, summary);
+    if (scan_reports) {  // first_record as one scan over the whole batch gives it
+        pcs_manifest_summary unused;
+        pcs::manifest_summarize(scan_reports, n_images, 0, &unused);
+    }
+    if (s && summary->n_rows_written) {
+        e = hipMemcpyAsync(table, d_table, summary->n_rows_written * 8, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+    }
+    if (tid >= 0) (void)pcs::scratch_release(tid, s ? s : slot.stream);
+    return finish(e, "manifest replay");
+}
+
+// pcs_scrub_live_host: one byte per page and the table go to the device, the
+// _dev form runs, the owners, the summary and the listed pages come back.
+int host_scrub_live(const uint8_t* cls, uint64_t n_pages, uint64_t fp_first, const uint64_t* table, uint64_t table_size,
+                    uint32_t* owner, pcs_live_summary* summary, pcs_live_page* damaged, uint64_t damaged_cap) {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return hip_fail(e, "hipGetDevice");
+    Slot& slot = t_ctx[dev].slot[0];
+    if (int rc = ensure_slot(slot, 1, 1)) return rc;
+    hipStream_t s = slot.stream;
+    const uint64_t cap = std::min(damaged_cap, n_pages);  // no more pages than the window holds are damaged
+    const uint64_t cls_bytes = (n_pages + 7) & ~uint64_t(7);
+    void* buf = nullptr;
+    int id = -1;
+    e = pcs::scratch_acquire(sizeof(pcs_live_summary) + table_size * 8 + cap * sizeof(pcs_live_page) + cls_bytes +
+                                 (owner ? n_pages * 4 : 0) + 8,
+                             &buf, &id);
+    pcs_live_summary* d_sum = static_cast<pcs_live_summary*>(buf);
+    uint64_t* d_table = reinterpret_cast<uint64_t*>(d_sum + 1);
+    pcs_live_page* d_list = reinterpret_cast<pcs_live_page*>(d_table + table_size);
+    uint8_t* d_cls = reinterpret_cast<uint8_t*>(d_list + cap);
+    uint32_t* d_owner = owner ? reinterpret_cast<uint32_t*>(d_cls + cls_bytes) : nullptr;
+    if (e == hipSuccess && n_pages) e = hipMemcpyAsync(d_cls, cls, n_pages, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && table_size) e = hipMemcpyAsync(d_table, table, table_size * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = pcs::run_scrub_live(d_cls, n_pages, fp_first, d_table, table_size, d_owner,
+                                reinterpret_cast<uint64_t*>(d_sum), reinterpret_cast<uint64_t*>(cap ? d_list : nullptr),
+                                cap, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(summary, d_sum, sizeof(*summary), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && owner && n_pages) e = hipMemcpyAsync(owner, d_owner, n_pages * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess && summary->n_listed) {
+        e = hipMemcpyAsync(damaged, d_list, summary->n_listed * sizeof(pcs_live_page), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+    }
+    if (id >= 0) (void)pcs::scratch_release(id, s);
+    if (e != hipSuccess) (void)hipStreamSynchronize(s);  // nothing of this call left in flight
+    if (e == hipSuccess) summary->n_listed = std::min(summary->n_damaged, damaged_cap);
+    return finish(e, "scrub live");
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -2373,6 +2496,62 @@ int pcs_manifest_scan_host(const void* const* images, const uint64_t* sizes, uin
     if (injected_failure()) return fail(PCS_ERR_HIP, "injected failure (PCS_TUNE_FAIL_INJECT)");
     if (int rc = require_device()) return rc;
     return host_manifest_scan(images, sizes, n_images, align, reports, summary, records, record_cap);
+}
+
+int pcs_manifest_replay_dev(const void* d_base, uint64_t total_bytes, const uint64_t* d_img_off,
+                            const uint64_t* d_img_size, uint64_t n_images, uint32_t align,
+                            pcs_manifest_report* d_scan_reports, pcs_replay_report* d_reports,
+                            pcs_replay_summary* d_summary, uint64_t* d_table, uint64_t table_cap, pcs_stream_t stream) {
+    static_assert(sizeof(pcs_replay_report) == 16 * sizeof(uint64_t), "pcs_replay_report is 16 x u64");
+    static_assert(sizeof(pcs_replay_summary) == 12 * sizeof(uint64_t), "pcs_replay_summary is 12 x u64");
+    if (const char* why = pcs::replay_dev_args(d_base, total_bytes, d_img_off, d_img_size, n_images, align,
+                                               d_scan_reports, d_reports, d_summary, d_table, table_cap))
+        return fail(PCS_ERR_INVALID, why);
+    if (int rc = require_device()) return rc;
+    return finish(pcs::run_manifest_replay(static_cast<const uint8_t*>(d_base), total_bytes, d_img_off, d_img_size,
+                                           n_images, align, reinterpret_cast<uint64_t*>(d_scan_reports),
+                                           reinterpret_cast<uint64_t*>(d_reports),
+                                           reinterpret_cast<uint64_t*>(d_summary), d_table, 0, table_cap,
+                                           reinterpret_cast<hipStream_t>(stream)),
+                  "manifest replay kernel launch");
+}
+
+int pcs_manifest_replay_host(const void* const* images, const uint64_t* sizes, uint64_t n_images, uint32_t align,
+                             pcs_manifest_report* scan_reports, pcs_replay_report* reports,
+                             pcs_replay_summary* summary, uint64_t* table, uint64_t table_cap) {
+    if (const char* why = pcs::replay_host_args(images, sizes, n_images, align, reports, summary, table, table_cap))
+        return fail(PCS_ERR_INVALID, why);
+    if (injected_failure()) return fail(PCS_ERR_HIP, "injected failure (PCS_TUNE_FAIL_INJECT)");
+    if (int rc = require_device()) return rc;
+    return host_manifest_replay(images, sizes, n_images, align, scan_reports, reports, summary, table, table_cap);
+}
+
+int pcs_scrub_live_dev(const uint8_t* d_class, uint64_t n_pages, uint64_t fp_first, const uint64_t* d_table,
+                       uint64_t table_size, uint32_t* d_owner, pcs_live_summary* d_summary, pcs_live_page* d_damaged,
+                       uint64_t damaged_cap, pcs_stream_t stream) {
+    static_assert(sizeof(pcs_live_page) == 16, "pcs_live_page is 16 bytes");
+    static_assert(sizeof(pcs_live_summary) == 16 * sizeof(uint64_t), "pcs_live_summary is 16 x u64");
+    if (const char* why = pcs::live_args(d_class, n_pages, fp_first, d_table, table_size, d_summary, d_damaged,
+                                         damaged_cap))
+        return fail(PCS_ERR_INVALID, why);
+    if (reinterpret_cast<uintptr_t>(d_table) % 8 || reinterpret_cast<uintptr_t>(d_summary) % 8 ||
+        reinterpret_cast<uintptr_t>(d_damaged) % 8 || reinterpret_cast<uintptr_t>(d_owner) % 4)
+        return fail(PCS_ERR_INVALID, "d_table, d_summary, d_damaged or d_owner is misaligned");
+    if (int rc = require_device()) return rc;
+    return finish(pcs::run_scrub_live(d_class, n_pages, fp_first, d_table, table_size, d_owner,
+                                      reinterpret_cast<uint64_t*>(d_summary), reinterpret_cast<uint64_t*>(d_damaged),
+                                      damaged_cap, reinterpret_cast<hipStream_t>(stream)),
+                  "scrub live kernel launch");
+}
+
+int pcs_scrub_live_host(const uint8_t* cls, uint64_t n_pages, uint64_t fp_first, const uint64_t* table,
+                        uint64_t table_size, uint32_t* owner, pcs_live_summary* summary, pcs_live_page* damaged,
+                        uint64_t damaged_cap) {
+    if (const char* why = pcs::live_args(cls, n_pages, fp_first, table, table_size, summary, damaged, damaged_cap))
+        return fail(PCS_ERR_INVALID, why);
+    if (injected_failure()) return fail(PCS_ERR_HIP, "injected failure (PCS_TUNE_FAIL_INJECT)");
+    if (int rc = require_device()) return rc;
+    return host_scrub_live(cls, n_pages, fp_first, table, table_size, owner, summary, damaged, damaged_cap);
 }
 
 int pcs_shard_range(uint64_t n, int world, int rank, uint64_t* begin, uint64_t* end) {

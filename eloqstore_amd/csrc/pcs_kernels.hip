@@ -1900,7 +1900,7 @@ uint64_t next_call_id() {
 // tuning knobs (pcs_set_tuning): read at every launch
 // ---------------------------------------------------------------------------
 namespace {
-constexpr int kTuneKeys = 39;
+constexpr int kTuneKeys = 40;
 // Keys retired in round 2 with the variants they selected (measured slower,
 // DESIGN.md §4): 4 XXH64 nt loads, 5 in-place stamp width, 10 descriptor tile
 // sort, 12 descriptor slices, 14 XXH64 descriptor sort; round-2 experiments
@@ -1918,7 +1918,7 @@ constexpr int kTuneKeys = 39;
 constexpr bool kRetired[kTuneKeys] = {false, false, false, false, true, true, false, false, false, false, true,  false,
                                       true,  false, true,  false, true,  true,  true,  true,  true,  true,  true,  false,
                                       false, true,  false, false, false, true,  false, false, true,  false,
-                                      false, false, false, /*37: never assigned*/ true, false};
+                                      false, false, false, /*37: never assigned*/ true, false, false};
 std::atomic<int64_t> g_tune[kTuneKeys] = {0, /*xxh3 blocks/CU*/ 0, /*xxh64 blocks/CU*/ 0, /*xxh3 nt*/ 1,
                                           /*retired*/ 0, /*retired*/ 0, /*xxh64 LDS depth (2/3/4/5 -> 1/2/4/3)*/ 0,
                                           /*zero copy*/ 1, /*xxh3 run-time size: 4-block batches*/ 1,
@@ -1948,10 +1948,13 @@ std::atomic<int64_t> g_tune[kTuneKeys] = {0, /*xxh3 blocks/CU*/ 0, /*xxh64 block
                                           /*sync host calls: microseconds of spinning before sleeping between checks (0 = spin)*/ 0,
                                           /*validate service: polls read the kernel's departure words*/ 1,
                                           /*never assigned*/ 0,
-                                          /*manifest scan: slots per LDS tile of the walk (power of two, 64..4096)*/ 2048};
+                                          /*manifest scan: slots per LDS tile of the walk (power of two, 64..4096)*/ 2048,
+                                          /*manifest replay: bytes of a mapping section per decode work item (power of two, 64..4096)*/ 4096};
 }
 int set_tuning(int key, int64_t value) {
     if (key <= 0 || key >= kTuneKeys || kRetired[key] || value < 0) return -1;
+    // the replay's tile is also the unit its scratch is sized by: only a power of two in [64, 4096]
+    if (key == 39 && (value < 64 || value > 4096 || (value & (value - 1)) != 0)) return -1;
     g_tune[key].store(value, std::memory_order_relaxed);
     return 0;
 }
@@ -3078,6 +3081,809 @@ hipError_t run_manifest_scan(const uint8_t* base, uint64_t total, const uint64_t
     }
     hipLaunchKernelGGL(k_mscan_summary, dim3(1), dim3(256), 0, s, n_images, ctl, reports, cap, summary);
     return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Manifest replay (pcs_manifest_replay_dev): what Replayer::Replay computes,
+// for every image of a batch.  The scan above runs first with a record array
+// in scratch, so every record's offset, length and ok flag are on the device.
+// A record's payload is a prelude (snapshot: varint64 max_fp_id, varint32
+// dict_len and the dict bytes) followed by LE32 mapping_len, the mapping
+// section, LE32 term_len and the term section; sections are runs of varints.
+// The decode is byte-parallel: a varint ends at every byte below 0x80, so the
+// ordinal of a varint in its section is the number of such bytes before it,
+// which a count per tile and two exclusive sums give.  Launches, ordered by
+// construction; the only atomics on global memory are max, min and integer
+// add, so the output is the same on every call:
+//   k_replay_sections  one block per image, a lane per replayed record: the
+//                      prelude with a bounds test before every read, up to two
+//                      sections (byte offset, length) per record;
+//   k_replay_plan      one block: exclusive sum of the sections' tile counts;
+//   k_replay_count     one wave per tile: 16 bytes per lane, terminators by
+//                      mask and popcount, one count per tile;
+//   k_replay_scan      one block: exclusive sum of the tile counts, so every
+//                      tile knows the ordinal of its first varint and every
+//                      section its varint count;
+//   k_replay_decode<1> one wave per tile: each terminator lane looks back at
+//                      most 10 bytes, never before its section's start, flags
+//                      over-long runs, folds 1 + the largest logged page id
+//                      and max_fp_id; the first tile of a section checks its
+//                      last byte and the parity of its count;
+//   k_replay_images    one block: status, table_size and its exclusive sum;
+//   k_replay_fill      rows to be written become 7, their sequence words 0;
+//   k_replay_decode<2> snapshot values go to their rows; a log entry does
+//                      atomicMax(seq[row], s), s = the global ordinal of its
+//                      value varint, which ascends in record, then byte order;
+//   k_replay_decode<3> the log entry whose s won stores its value;
+//   k_replay_stats     one lane per written row: mapped rows, smallest and
+//                      largest file page, file pages at or above max_fp_id;
+//   k_replay_report    one block: the reports and the summary.
+// ---------------------------------------------------------------------------
+constexpr int kReplayReportWords = 16;   // pcs_replay_report
+constexpr int kReplaySummaryWords = 12;  // pcs_replay_summary
+constexpr int kReplayCtlWords = 8;       // ctl: invalid image, records, tiles, rows, rows written
+constexpr uint64_t kReplayInvalidValue = 7;  // MappingSnapshot::InvalidValue
+constexpr uint32_t kReplayDefaultTile = 4096;  // profiles/replay/replay_rate.txt
+constexpr uint64_t kReplayOk = 0, kReplayNotReplayable = 1, kReplayMalformed = 2, kReplayTableCap = 3;
+
+// per-image words (u64), kReplayImgWords each
+constexpr int kRiBad = 0;     // lowest record with a violation, ~0 when none (atomicMin)
+constexpr int kRiMaxPid = 1;  // 1 + largest page id of a replayed log entry (atomicMax)
+constexpr int kRiMaxFp = 2;   // max_fp_id (the snapshot's, then atomicMax)
+constexpr int kRiDict = 3;    // dict_len
+constexpr int kRiSnap = 4;    // varints in the snapshot's mapping section
+constexpr int kRiLog = 5;     // log entries (atomicAdd)
+constexpr int kRiTerm = 6;    // term pairs (atomicAdd)
+constexpr int kRiNrep = 7;    // records replayed
+constexpr int kRiStatus = 8;
+constexpr int kRiSize = 9;    // table_size
+constexpr int kRiFirst = 10;  // table_first
+constexpr int kRiMapped = 11, kRiMinFp = 12, kRiMaxMapped = 13, kRiBeyond = 14;  // k_replay_stats
+constexpr int kReplayImgWords = 16;
+
+uint32_t replay_tile() {
+    const int64_t t = g_tune[39].load(std::memory_order_relaxed);
+    if (t < 64 || t > 4096 || (t & (t - 1)) != 0) return kReplayDefaultTile;
+    return (uint32_t)t;
+}
+
+// A varint of at most `limit` bytes at p[pos ..), inside [0, L): false when it
+// does not end within its limit or within L.
+__device__ __forceinline__ bool replay_varint(const uint8_t* p, uint64_t L, uint64_t& pos, int limit, uint64_t& v) {
+    v = 0;
+    for (int n = 0;; ++n) {
+        if (pos >= L || n == limit) return false;
+        const uint8_t b = p[pos++];
+        v |= (uint64_t)(b & 0x7F) << (7 * n);  // n = 9: only bit 0 stays, the rest wraps away
+        if (b < 0x80) return true;
+    }
+}
+__device__ __forceinline__ uint32_t replay_le32(const uint8_t* p) {
+    return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
+}
+
+// sec_off / sec_len: two sections per record g (2g mapping, 2g + 1 term)
+__global__ __launch_bounds__(256) void k_replay_sections(const uint8_t* __restrict__ base, const uint64_t* __restrict__ off,
+                                                        uint64_t n_images, const uint64_t* __restrict__ scan_sum,
+                                                        const uint64_t* __restrict__ scan_rep,
+                                                        const uint64_t* __restrict__ recs, uint64_t* __restrict__ ctl,
+                                                        uint64_t* __restrict__ img, uint32_t* __restrict__ rec_img,
+                                                        uint32_t* __restrict__ rec_k, uint32_t* __restrict__ sec_off,
+                                                        uint32_t* __restrict__ sec_len) {
+    const uint64_t invalid = scan_sum[11];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        ctl[0] = invalid;
+        ctl[1] = invalid == ~0ull ? scan_sum[1] : 0;
+        ctl[2] = ctl[3] = ctl[4] = 0;
+    }
+    if (invalid != ~0ull || blockIdx.x >= n_images) return;  // uniform over the block
+    const uint64_t i = blockIdx.x;
+    const uint64_t* rep = scan_rep + i * kMscanReportWords;
+    const uint64_t n_rec = rep[1], fc = rep[4], verdict = rep[9], r0 = rep[10];
+    const uint64_t n_rep = verdict <= 1 ? (fc == ~0ull ? n_rec : fc) : 0;  // CLEAN or TORN_TAIL
+    uint64_t* im = img + i * kReplayImgWords;
+    if (threadIdx.x < kReplayImgWords)
+        im[threadIdx.x] = threadIdx.x == kRiBad ? ~0ull : threadIdx.x == kRiNrep ? n_rep : threadIdx.x == kRiMinFp ? ~0ull : 0;
+    __syncthreads();
+    for (uint64_t k = threadIdx.x; k < n_rec; k += 256) {
+        const uint64_t g = r0 + k;
+        uint32_t mo = 0, ml = 0, to = 0, tl = 0;
+        if (k < n_rep) {
+            const uint64_t* e = recs + g * kMscanRecordWords;
+            const uint64_t pay = off[i] + e[0] + kMscanHeader;  // the scan found the record inside its image
+            const uint64_t L = e[3] & 0xFFFFFFFFull;
+            const uint8_t* p = base + pay;
+            uint64_t pos = 0, maxfp = 0, dict = 0;
+            bool ok = true;
+            if (k == 0) {
+                ok = replay_varint(p, L, pos, 10, maxfp);
+                ok = ok && replay_varint(p, L, pos, 5, dict);
+                dict &= 0xFFFFFFFFull;
+                ok = ok && dict <= L - pos;
+                if (ok) pos += dict;
+            }
+            const uint64_t rem = ok ? L - pos : 0;
+            ok = ok && rem >= 8;
+            if (ok) {
+                const uint64_t mlen = replay_le32(p + pos);
+                if (mlen + 8 > rem) {
+                    ok = false;
+                } else {
+                    const uint64_t tlen = replay_le32(p + pos + 4 + mlen);
+                    if (tlen > rem - mlen - 8) {
+                        ok = false;
+                    } else {
+                        mo = (uint32_t)(pay + pos + 4);  // total_bytes < 2^32
+                        ml = (uint32_t)mlen;
+                        to = (uint32_t)(pay + pos + 8 + mlen);
+                        tl = (uint32_t)tlen;
+                    }
+                }
+            }
+            if (!ok) atomicMin(reinterpret_cast<unsigned long long*>(im + kRiBad), (unsigned long long)k);
+            if (k == 0 && ok) {
+                im[kRiMaxFp] = maxfp;
+                im[kRiDict] = dict;
+            }
+        }
+        rec_img[g] = (uint32_t)i;
+        rec_k[g] = (uint32_t)k;
+        sec_off[2 * g] = mo;
+        sec_len[2 * g] = ml;
+        sec_off[2 * g + 1] = to;
+        sec_len[2 * g + 1] = tl;
+    }
+}
+
+// out[j] = exclusive sum over j < n of f(j); out[n] = the total, also into *total_out
+template <typename F>
+__device__ __forceinline__ void replay_block_scan(uint64_t n, F f, uint32_t* __restrict__ out, uint64_t* total_out) {
+    __shared__ uint64_t w4[4];
+    uint64_t run = 0;  // the sum of the rounds before this one (uniform)
+    for (uint64_t b0 = 0; b0 < n; b0 += 256 * 4) {
+        const uint64_t j0 = b0 + threadIdx.x * 4u;  // four consecutive items per thread
+        uint64_t c[4], mine = 0;
+#pragma unroll
+        for (int x = 0; x < 4; ++x) {
+            c[x] = j0 + x < n ? f(j0 + x) : 0;
+            mine += c[x];
+        }
+        uint64_t t;
+        uint64_t before = run + block_excl_scan(mine, w4, t);
+#pragma unroll
+        for (int x = 0; x < 4; ++x) {
+            if (j0 + x < n) out[j0 + x] = (uint32_t)before;
+            before += c[x];
+        }
+        run += t;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        out[n] = (uint32_t)run;
+        if (total_out) *total_out = run;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_replay_plan(uint64_t* __restrict__ ctl, uint32_t tile_shift,
+                                                    const uint32_t* __restrict__ sec_len,
+                                                    uint32_t* __restrict__ sec_tile) {
+    if (ctl[0] != ~0ull) return;
+    const uint64_t mask = (1ull << tile_shift) - 1;
+    replay_block_scan(2 * ctl[1], [&](uint64_t q) { return ((uint64_t)sec_len[q] + mask) >> tile_shift; }, sec_tile,
+                      ctl + 2);
+}
+
+__global__ __launch_bounds__(256) void k_replay_scan(const uint64_t* __restrict__ ctl, const uint32_t* __restrict__ tile_cnt,
+                                                    uint32_t* __restrict__ tile_pre) {
+    if (ctl[0] != ~0ull) return;
+    replay_block_scan(ctl[2], [&](uint64_t t) { return (uint64_t)tile_cnt[t]; }, tile_pre, nullptr);
+}
+
+// the section that holds tile t: the last q below n_sec with sec_tile[q] <= t
+__device__ __forceinline__ uint64_t replay_section_of(const uint32_t* __restrict__ sec_tile, uint64_t n_sec, uint64_t t) {
+    uint64_t lo = 0, hi = n_sec;
+    while (hi - lo > 1) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (sec_tile[mid] <= t) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// bit k set: byte k of the 16 is below 0x80 (a varint ends there)
+__device__ __forceinline__ uint32_t replay_term_mask(uint64_t lo, uint64_t hi) {
+    uint32_t m = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) m |= (byte_of(lo, hi, k) < 0x80 ? 1u : 0u) << k;
+    return m;
+}
+
+__global__ __launch_bounds__(256) void k_replay_count(const uint8_t* __restrict__ base, const uint64_t* __restrict__ ctl,
+                                                     uint32_t tile_shift, const uint32_t* __restrict__ sec_off,
+                                                     const uint32_t* __restrict__ sec_len,
+                                                     const uint32_t* __restrict__ sec_tile,
+                                                     uint32_t* __restrict__ tile_cnt) {
+    if (ctl[0] != ~0ull) return;
+    const uint64_t n_tiles = ctl[2], n_sec = 2 * ctl[1];
+    const uint64_t tile = 1ull << tile_shift;
+    const int lane = threadIdx.x & 63;
+    const uint64_t stride = (uint64_t)gridDim.x * 4;
+    for (uint64_t t = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); t < n_tiles; t += stride) {
+        const uint64_t q = replay_section_of(sec_tile, n_sec, t);
+        const uint8_t* sec = base + sec_off[q];
+        const uint64_t len = sec_len[q];
+        const uint64_t start = (t - sec_tile[q]) << tile_shift, end = min(start + tile, len);
+        uint64_t c = 0;
+        for (uint64_t P = start + lane * 16u; P < end; P += 1024) {
+            uint64_t lo, hi;
+            ld_bytes16(sec + P, end - P, 0x80, lo, hi);
+            c += __builtin_popcount(replay_term_mask(lo, hi));
+        }
+        c = wave_sum(c);
+        if (lane == 0) tile_cnt[t] = (uint32_t)c;
+    }
+}
+
+// The varint that ends at sec[pos]: its length, limit + 1 when the run of
+// continuation bytes before it is longer than the limit allows; never reads
+// before sec[0].
+__device__ __forceinline__ int replay_run(const uint8_t* sec, uint64_t pos, int limit) {
+    int len = 1;
+    while (len <= limit && pos >= (uint64_t)len && sec[pos - len] >= 0x80) ++len;
+    return len;
+}
+__device__ __forceinline__ uint64_t replay_value(const uint8_t* sec, uint64_t pos, int len) {
+    uint64_t v = 0;
+    for (int x = 0; x < len; ++x) v |= (uint64_t)(sec[pos - len + 1 + x] & 0x7F) << (7 * x);
+    return v;
+}
+
+// MODE 1 checks and folds, MODE 2 stores snapshot values and bids for log
+// rows, MODE 3 stores the winning log entries.
+template <int MODE>
+__global__ __launch_bounds__(256) void k_replay_decode(const uint8_t* __restrict__ base, const uint64_t* __restrict__ ctl,
+                                                      uint32_t tile_shift, const uint32_t* __restrict__ sec_off,
+                                                      const uint32_t* __restrict__ sec_len,
+                                                      const uint32_t* __restrict__ sec_tile,
+                                                      const uint32_t* __restrict__ rec_img,
+                                                      const uint32_t* __restrict__ rec_k,
+                                                      const uint32_t* __restrict__ tile_pre, uint64_t* __restrict__ img,
+                                                      uint64_t* __restrict__ table, uint32_t* __restrict__ seq) {
+    if (ctl[0] != ~0ull) return;
+    const uint64_t n_tiles = ctl[2], n_sec = 2 * ctl[1];
+    const uint64_t tile = 1ull << tile_shift;
+    const int lane = threadIdx.x & 63;
+    const uint64_t stride = (uint64_t)gridDim.x * 4;
+    for (uint64_t t = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); t < n_tiles; t += stride) {
+        // everything up to the byte loop is uniform over the wave
+        const uint64_t q = replay_section_of(sec_tile, n_sec, t);
+        const uint64_t g = q >> 1, k = rec_k[g];
+        const int kind = (q & 1) ? 2 : k == 0 ? 0 : 1;  // snapshot mapping, log mapping, term
+        uint64_t* im = img + (uint64_t)rec_img[g] * kReplayImgWords;
+        if (MODE >= 2 && (kind == 2 || im[kRiStatus] != kReplayOk)) continue;
+        if (MODE == 3 && kind == 0) continue;
+        const uint8_t* sec = base + sec_off[q];
+        const uint64_t len = sec_len[q];
+        const uint64_t t0 = sec_tile[q];
+        const uint64_t start = (t - t0) << tile_shift, end = min(start + tile, len);
+        const uint64_t sec_ord = tile_pre[t0];  // global ordinal of the section's first varint
+        const uint64_t tf = MODE >= 2 ? im[kRiFirst] : 0;
+        bool bad = false;
+        uint64_t max_pid = 0, max_fp = 0;
+        if (MODE == 1 && t == t0 && lane == 0) {
+            const uint64_t cnt = tile_pre[sec_tile[q + 1]] - sec_ord;
+            bad = sec[len - 1] >= 0x80 || (kind != 0 && (cnt & 1));  // a tile exists, so len >= 1
+            if (kind == 0) im[kRiSnap] = cnt;
+            else if (cnt >= 2)
+                atomicAdd(reinterpret_cast<unsigned long long*>(im + (kind == 1 ? kRiLog : kRiTerm)),
+                          (unsigned long long)(cnt / 2));
+        }
+        uint64_t ord = tile_pre[t] - sec_ord;  // ordinal in the section of the tile's first varint
+        for (uint64_t p0 = start; p0 < end; p0 += 1024) {
+            const uint64_t P = p0 + lane * 16u;
+            uint64_t lo, hi;
+            ld_bytes16(sec + P, P < end ? end - P : 0, 0x80, lo, hi);
+            uint32_t mask = replay_term_mask(lo, hi);
+            uint64_t tot;
+            uint64_t o = ord + wave_excl_scan((uint64_t)__builtin_popcount(mask), tot);
+            ord += tot;
+            for (; mask; mask &= mask - 1, ++o) {
+                const uint64_t pos = P + __builtin_ctz(mask);
+                const bool is_pid = kind == 1 && (o & 1) == 0;
+                const int limit = is_pid ? 5 : 10;
+                const int n = replay_run(sec, pos, limit);
+                if (n > limit) {
+                    bad = true;
+                    continue;
+                }
+                if (kind == 2 || is_pid) continue;  // a page id is read with its value
+                if (kind == 0) {
+                    if (MODE == 2) table[tf + o] = replay_value(sec, pos, n);
+                    continue;
+                }
+                const uint64_t v = replay_value(sec, pos, n);
+                if (pos < (uint64_t)n) continue;  // no page id before the value: an over-long run was flagged
+                const uint64_t ppos = pos - n;
+                const int pn = replay_run(sec, ppos, 5);
+                if (pn > 5) continue;  // flagged at the page id
+                const uint64_t pid = replay_value(sec, ppos, pn) & 0xFFFFFFFFull;
+                if (MODE == 1) {
+                    max_pid = max(max_pid, pid + 1);
+                    if ((v & 7) == 1) max_fp = max(max_fp, (v >> 3) + 1);
+                } else {
+                    const uint32_t s = (uint32_t)(sec_ord + o);  // odd ordinal in the section: never 0
+                    if (MODE == 2) atomicMax(seq + tf + pid, s);
+                    else if (seq[tf + pid] == s) table[tf + pid] = v;
+                }
+            }
+        }
+        if (MODE == 1) {
+            const bool any_bad = __any(bad);
+            max_pid = wave_max(max_pid);
+            max_fp = wave_max(max_fp);
+            if (lane == 0) {
+                if (any_bad) atomicMin(reinterpret_cast<unsigned long long*>(im + kRiBad), (unsigned long long)k);
+                if (max_pid) atomicMax(reinterpret_cast<unsigned long long*>(im + kRiMaxPid), (unsigned long long)max_pid);
+                if (max_fp) atomicMax(reinterpret_cast<unsigned long long*>(im + kRiMaxFp), (unsigned long long)max_fp);
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_replay_images(uint64_t n_images, const uint64_t* __restrict__ scan_rep,
+                                                      uint64_t* __restrict__ ctl, uint64_t* __restrict__ img,
+                                                      uint64_t table_base, uint64_t table_cap) {
+    __shared__ uint64_t w4[4];
+    if (ctl[0] != ~0ull) return;
+    uint64_t rows = 0, written = 0;  // of the images before this round (uniform)
+    for (uint64_t b0 = 0; b0 < n_images; b0 += 256) {
+        const uint64_t i = b0 + threadIdx.x;
+        uint64_t size = 0, status = kReplayNotReplayable;
+        uint64_t* im = img + i * kReplayImgWords;
+        if (i < n_images) {
+            const uint64_t verdict = scan_rep[i * kMscanReportWords + 9];
+            if (verdict <= 1) {
+                status = im[kRiBad] != ~0ull ? kReplayMalformed : kReplayOk;
+                if (status == kReplayOk) size = max(im[kRiSnap], im[kRiMaxPid]);
+            }
+        }
+        uint64_t t;
+        const uint64_t first = table_base + rows + block_excl_scan(size, w4, t);
+        rows += t;
+        __syncthreads();
+        if (i < n_images && status == kReplayOk && first + size > table_cap) status = kReplayTableCap;
+        const uint64_t w = status == kReplayOk ? size : 0;
+        uint64_t tw;
+        (void)block_excl_scan(w, w4, tw);
+        written += tw;
+        if (i < n_images) {
+            im[kRiStatus] = status;
+            im[kRiSize] = size;
+            im[kRiFirst] = first;
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        ctl[3] = rows;
+        ctl[4] = written;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_replay_fill(const uint64_t* __restrict__ ctl, uint64_t table_base,
+                                                    uint64_t* __restrict__ table, uint32_t* __restrict__ seq) {
+    if (ctl[0] != ~0ull) return;
+    const uint64_t n = ctl[4];
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += stride) {
+        table[table_base + r] = kReplayInvalidValue;
+        seq[table_base + r] = 0;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_replay_stats(uint64_t n_images, const uint64_t* __restrict__ ctl,
+                                                     uint64_t table_base, const uint64_t* __restrict__ table,
+                                                     uint64_t* __restrict__ img) {
+    if (ctl[0] != ~0ull) return;
+    const uint64_t n = ctl[4];
+    const int lane = threadIdx.x & 63;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t r0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) & ~63ull; r0 < n; r0 += stride) {
+        const uint64_t r = r0 + lane;
+        const bool valid = r < n;
+        uint64_t i = 0, mapped = 0, lo_fp = ~0ull, hi_fp = 0, beyond = 0;
+        if (valid) {
+            const uint64_t row = table_base + r;
+            // the image that holds the row: the last i with table_first <= row (an image after
+            // the holder starts at or after the holder's end, whatever its status)
+            uint64_t a = 0, b = n_images;
+            while (b - a > 1) {
+                const uint64_t mid = a + (b - a) / 2;
+                if (img[mid * kReplayImgWords + kRiFirst] <= row) a = mid;
+                else b = mid;
+            }
+            i = a;
+            const uint64_t v = table[row];
+            if ((v & 7) == 1) {
+                const uint64_t id = v >> 3;
+                mapped = 1;
+                lo_fp = hi_fp = id;
+                beyond = id >= img[i * kReplayImgWords + kRiMaxFp] ? 1 : 0;
+            }
+        }
+        const uint64_t i0 = __shfl((unsigned long long)i, 0, 64);  // lane 0 of a live wave is valid
+        unsigned long long* im = reinterpret_cast<unsigned long long*>(img + i * kReplayImgWords);
+        if (__all(!valid || i == i0)) {  // one image over the wave: one set of atomics
+            mapped = wave_sum(mapped);
+            beyond = wave_sum(beyond);
+            lo_fp = wave_min(lo_fp);
+            hi_fp = wave_max(hi_fp);
+            if (lane == 0 && mapped) {
+                atomicAdd(im + kRiMapped, (unsigned long long)mapped);
+                atomicMin(im + kRiMinFp, (unsigned long long)lo_fp);
+                atomicMax(im + kRiMaxMapped, (unsigned long long)hi_fp);
+                if (beyond) atomicAdd(im + kRiBeyond, (unsigned long long)beyond);
+            }
+        } else if (mapped) {
+            atomicAdd(im + kRiMapped, 1ull);
+            atomicMin(im + kRiMinFp, (unsigned long long)lo_fp);
+            atomicMax(im + kRiMaxMapped, (unsigned long long)hi_fp);
+            if (beyond) atomicAdd(im + kRiBeyond, 1ull);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_replay_report(uint64_t n_images, const uint64_t* __restrict__ ctl,
+                                                      const uint64_t* __restrict__ scan_rep,
+                                                      const uint64_t* __restrict__ recs, const uint64_t* __restrict__ img,
+                                                      uint64_t* __restrict__ reports, uint64_t* __restrict__ summary) {
+    __shared__ unsigned long long tot[7];  // images by status 0..3, mapped, log entries, first bad image
+    const uint64_t invalid = ctl[0];
+    if (invalid != ~0ull) {  // uniform: only n_images and the invalid image are reported
+        if (threadIdx.x < kReplaySummaryWords)
+            summary[threadIdx.x] = threadIdx.x == 0 ? n_images : threadIdx.x == 10 ? invalid : 0;
+        return;
+    }
+    if (threadIdx.x < 7) tot[threadIdx.x] = threadIdx.x == 6 ? ~0ull : 0ull;
+    __syncthreads();
+    uint64_t acc[6] = {};
+    uint64_t first_bad = ~0ull;
+    for (uint64_t i = threadIdx.x; i < n_images; i += 256) {
+        const uint64_t* im = img + i * kReplayImgWords;
+        const uint64_t status = im[kRiStatus];
+        const bool counted = status == kReplayOk || status == kReplayTableCap;
+        const bool ok = status == kReplayOk;
+        uint64_t root = 0, ttl = 0;
+        if (counted) {
+            const uint64_t* e = recs + (scan_rep[i * kMscanReportWords + 10] + im[kRiNrep] - 1) * kMscanRecordWords;
+            root = e[3] >> 32;
+            ttl = e[4] & 0xFFFFFFFFull;
+        }
+        uint64_t* r = reports + i * kReplayReportWords;
+        r[0] = status;
+        r[1] = im[kRiNrep];
+        r[2] = status == kReplayMalformed ? im[kRiBad] : ~0ull;
+        r[3] = root;
+        r[4] = ttl;
+        r[5] = counted ? im[kRiMaxFp] : 0;
+        r[6] = counted ? im[kRiDict] : 0;
+        r[7] = counted ? im[kRiSnap] : 0;
+        r[8] = counted ? im[kRiLog] : 0;
+        r[9] = im[kRiSize];
+        r[10] = im[kRiFirst];
+        r[11] = ok ? im[kRiMapped] : 0;
+        r[12] = ok && im[kRiMapped] ? im[kRiMinFp] : ~0ull;
+        r[13] = ok && im[kRiMapped] ? im[kRiMaxMapped] : ~0ull;
+        r[14] = ok ? im[kRiBeyond] : 0;
+        r[15] = counted ? im[kRiTerm] : 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc[k] += status == (uint64_t)k ? 1 : 0;
+        acc[4] += r[11];
+        acc[5] += r[8];
+        if (!ok && first_bad == ~0ull) first_bad = i;
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const uint64_t v = wave_sum(acc[k]);
+        if ((threadIdx.x & 63) == 0 && v) atomicAdd(&tot[k], (unsigned long long)v);
+    }
+    if (first_bad != ~0ull) atomicMin(&tot[6], (unsigned long long)first_bad);
+    __syncthreads();
+    if (threadIdx.x < kReplaySummaryWords) {
+        uint64_t v = 0;
+        switch (threadIdx.x) {
+            case 0: v = n_images; break;
+            case 1: case 2: case 3: case 4: v = tot[threadIdx.x - 1]; break;
+            case 5: v = ctl[3]; break;
+            case 6: v = ctl[4]; break;
+            case 7: v = tot[4]; break;
+            case 8: v = tot[5]; break;
+            case 9: v = tot[6]; break;
+            case 10: v = ~0ull; break;
+            default: v = 0; break;
+        }
+        summary[threadIdx.x] = v;
+    }
+}
+
+hipError_t run_manifest_replay(const uint8_t* base, uint64_t total, const uint64_t* off, const uint64_t* size,
+                               uint64_t n_images, uint32_t align, uint64_t* scan_reports, uint64_t* reports,
+                               uint64_t* summary, uint64_t* table, uint64_t table_base, uint64_t table_cap,
+                               hipStream_t s) {
+    uint32_t shift = 0;
+    while ((1u << shift) < align) ++shift;
+    const uint32_t tile = replay_tile();
+    uint32_t tile_shift = 0;
+    while ((1u << tile_shift) < tile) ++tile_shift;
+    if (total >= (1ull << 32) || n_images > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const uint64_t max_recs = (total >> shift) + n_images;             // the scan's own bound
+    const uint64_t max_tiles = (total >> tile_shift) + 2 * max_recs;  // sections are disjoint byte ranges
+    ScratchLease scratch(s);
+    // u64: ctl, scan summary, scan reports (when the caller wants none), records, image words;
+    // u32: rec_img, rec_k [max_recs], sec_off, sec_len [2 max_recs], sec_tile [2 max_recs + 1],
+    //      tile_cnt [max_tiles], tile_pre [max_tiles + 1], seq [table_cap]
+    const size_t words = kReplayCtlWords + kMscanSummaryWords + (scan_reports ? 0 : kMscanReportWords * n_images) +
+                         kMscanRecordWords * max_recs + kReplayImgWords * n_images;
+    const size_t u32s = 8 * max_recs + 2 * max_tiles + 4 + (table_cap > table_base ? table_cap : 0);
+    hipError_t e = scratch.get(words * 8 + u32s * 4);
+    if (e != hipSuccess) return e;
+    uint64_t* ctl = static_cast<uint64_t*>(scratch.p);
+    uint64_t* scan_sum = ctl + kReplayCtlWords;
+    uint64_t* scan_rep = scan_sum + kMscanSummaryWords;
+    uint64_t* recs = scan_rep + (scan_reports ? 0 : kMscanReportWords * n_images);
+    if (scan_reports) scan_rep = scan_reports;
+    uint64_t* img = recs + kMscanRecordWords * max_recs;
+    uint32_t* rec_img = reinterpret_cast<uint32_t*>(img + kReplayImgWords * n_images);
+    uint32_t* rec_k = rec_img + max_recs;
+    uint32_t* sec_off = rec_k + max_recs;
+    uint32_t* sec_len = sec_off + 2 * max_recs;
+    uint32_t* sec_tile = sec_len + 2 * max_recs;
+    uint32_t* tile_cnt = sec_tile + 2 * max_recs + 1;
+    uint32_t* tile_pre = tile_cnt + max_tiles;
+    uint32_t* seq = tile_pre + max_tiles + 1;
+    e = run_manifest_scan(base, total, off, size, n_images, align, scan_rep, scan_sum, recs, max_recs, s);
+    if (e != hipSuccess) return e;
+    if (n_images) {
+        const unsigned tgrid = grid_for(max_tiles, 4, kBlocksPerCu);
+        hipLaunchKernelGGL(k_replay_sections, dim3((unsigned)n_images), dim3(256), 0, s, base, off, n_images, scan_sum,
+                           scan_rep, recs, ctl, img, rec_img, rec_k, sec_off, sec_len);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_replay_plan, dim3(1), dim3(256), 0, s, ctl, tile_shift, sec_len, sec_tile);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_replay_count, dim3(tgrid), dim3(256), 0, s, base, ctl, tile_shift, sec_off, sec_len,
+                           sec_tile, tile_cnt);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_replay_scan, dim3(1), dim3(256), 0, s, ctl, tile_cnt, tile_pre);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_replay_decode<1>, dim3(tgrid), dim3(256), 0, s, base, ctl, tile_shift, sec_off, sec_len,
+                           sec_tile, rec_img, rec_k, tile_pre, img, table, seq);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_replay_images, dim3(1), dim3(256), 0, s, n_images, scan_rep, ctl, img, table_base,
+                           table_cap);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if (table_cap > table_base) {  // otherwise no image can be OK with rows to write
+            const unsigned rgrid = grid_for(table_cap - table_base, kBlock, kBlocksPerCu);
+            hipLaunchKernelGGL(k_replay_fill, dim3(rgrid), dim3(256), 0, s, ctl, table_base, table, seq);
+            if ((e = hipGetLastError()) != hipSuccess) return e;
+            hipLaunchKernelGGL(k_replay_decode<2>, dim3(tgrid), dim3(256), 0, s, base, ctl, tile_shift, sec_off, sec_len,
+                               sec_tile, rec_img, rec_k, tile_pre, img, table, seq);
+            if ((e = hipGetLastError()) != hipSuccess) return e;
+            hipLaunchKernelGGL(k_replay_decode<3>, dim3(tgrid), dim3(256), 0, s, base, ctl, tile_shift, sec_off, sec_len,
+                               sec_tile, rec_img, rec_k, tile_pre, img, table, seq);
+            if ((e = hipGetLastError()) != hipSuccess) return e;
+            hipLaunchKernelGGL(k_replay_stats, dim3(rgrid), dim3(256), 0, s, n_images, ctl, table_base, table, img);
+            if ((e = hipGetLastError()) != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL(k_replay_report, dim3(1), dim3(256), 0, s, n_images, ctl, scan_rep, recs, img, reports,
+                           summary);
+        return hipGetLastError();
+    }
+    // no image: the scan's summary says so; the replay's own is all zero but for "none"
+    hipLaunchKernelGGL(k_replay_sections, dim3(1), dim3(256), 0, s, base, off, n_images, scan_sum, scan_rep, recs,
+                       ctl, img, rec_img, rec_k, sec_off, sec_len);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_replay_report, dim3(1), dim3(256), 0, s, n_images, ctl, scan_rep, recs, img, reports, summary);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Scrub live (pcs_scrub_live_dev): which file pages of a window a replayed
+// mapping table still points to, who owns each, and the class census of the
+// live and the dead set.  A row v maps file page v >> 3 iff (v & 7) == 1.
+//   k_live_fill   owner[i] = UINT32_MAX, the three counters 0;
+//   k_live_owner  one lane per table row: atomicMin(owner[page], row) for rows
+//                 that point into the window, counts of mapped rows;
+//   k_live_count  one block per kScrubSpan pages: the six live/dead x class
+//                 cells, damaged live pages, first damaged, last live;
+//   k_live_scan   one block: each span's rank in the damaged list, summary;
+//   k_live_list   the spans whose rank is below the cap write their damaged
+//                 pages at rank + position (the scrub list's pattern: ascending
+//                 and the same on every call).
+// ---------------------------------------------------------------------------
+constexpr int kLiveRec = 10;           // u32 per span: damaged, live ok/blank/corrupt, dead ok/blank/corrupt, first damaged, last live + 1, live
+constexpr int kLiveSummaryWords = 16;  // pcs_live_summary
+
+__global__ __launch_bounds__(256) void k_live_fill(uint64_t n, uint32_t* __restrict__ owner, uint64_t* __restrict__ ctl) {
+    if (blockIdx.x == 0 && threadIdx.x < 4) ctl[threadIdx.x] = 0;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) owner[i] = 0xFFFFFFFFu;
+}
+
+__global__ __launch_bounds__(256) void k_live_owner(const uint64_t* __restrict__ table, uint64_t rows, uint64_t fp_first,
+                                                   uint64_t n, uint32_t* __restrict__ owner, uint64_t* __restrict__ ctl) {
+    uint64_t mapped = 0, inside = 0;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; p < rows; p += stride) {
+        const uint64_t v = table[p];
+        if ((v & 7) != 1) continue;
+        ++mapped;
+        const uint64_t id = v >> 3;
+        if (id >= fp_first && id - fp_first < n) {
+            ++inside;
+            atomicMin(owner + (id - fp_first), (uint32_t)p);
+        }
+    }
+    mapped = wave_sum(mapped);
+    inside = wave_sum(inside);
+    if ((threadIdx.x & 63) == 0) {
+        if (mapped) atomicAdd(reinterpret_cast<unsigned long long*>(ctl), (unsigned long long)mapped);
+        if (inside) atomicAdd(reinterpret_cast<unsigned long long*>(ctl + 1), (unsigned long long)inside);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_live_count(const uint8_t* __restrict__ cls, const uint32_t* __restrict__ owner,
+                                                   uint64_t n, uint32_t* __restrict__ rec) {
+    __shared__ uint32_t cnt[kLiveRec];
+    if (threadIdx.x < kLiveRec) cnt[threadIdx.x] = threadIdx.x == 7 ? 0xFFFFFFFFu : 0u;
+    __syncthreads();
+    const uint64_t p0 = (uint64_t)blockIdx.x * kScrubSpan + threadIdx.x * 16u;
+    uint32_t c7[7] = {};
+    uint32_t first = 0xFFFFFFFFu, last = 0, n_live = 0;
+    if (p0 < n) {
+        uint64_t cl, ch;
+        ld_bytes16(cls + p0, n - p0, 0xFF, cl, ch);
+        const int m = (int)min((uint64_t)16, n - p0);
+        for (int k = 0; k < m; ++k) {
+            const uint32_t c = byte_of(cl, ch, k);
+            const bool live = owner[p0 + k] != 0xFFFFFFFFu;
+            if (c <= kClassBlank) ++c7[(live ? 1 : 4) + (c == kClassOk ? 0 : c == kClassBlank ? 1 : 2)];
+            if (live) {
+                ++n_live;
+                last = threadIdx.x * 16u + k + 1;
+                if (c != kClassOk) {
+                    ++c7[0];
+                    if (first == 0xFFFFFFFFu) first = threadIdx.x * 16u + k;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int f = 0; f < 7; ++f) {
+        const uint32_t v = (uint32_t)wave_sum(c7[f]);
+        if ((threadIdx.x & 63) == 0 && v) atomicAdd(&cnt[f], v);
+    }
+    n_live = (uint32_t)wave_sum(n_live);
+    if ((threadIdx.x & 63) == 0 && n_live) atomicAdd(&cnt[9], n_live);
+    if (first != 0xFFFFFFFFu) atomicMin(&cnt[7], first);
+    if (last) atomicMax(&cnt[8], last);
+    __syncthreads();
+    if (threadIdx.x < kLiveRec) rec[(uint64_t)blockIdx.x * kLiveRec + threadIdx.x] = cnt[threadIdx.x];
+}
+
+__global__ __launch_bounds__(256) void k_live_scan(const uint32_t* __restrict__ rec, uint64_t nblocks, uint64_t n,
+                                                  uint64_t rows, uint64_t cap, const uint64_t* __restrict__ ctl,
+                                                  uint64_t* __restrict__ rank, uint64_t* __restrict__ summary) {
+    __shared__ uint64_t w4[4];
+    __shared__ unsigned long long tot[9];  // six cells, first damaged, last live + 1, live pages
+    if (threadIdx.x < 9) tot[threadIdx.x] = threadIdx.x == 6 ? ~0ull : 0ull;
+    __syncthreads();
+    uint64_t damaged = 0;  // in the spans before this round (uniform)
+    uint64_t acc[6] = {}, live = 0;
+    uint64_t first = ~0ull, last = 0;
+    for (uint64_t base = 0; base < nblocks; base += 256) {
+        const uint64_t b = base + threadIdx.x;
+        uint64_t c = 0;
+        if (b < nblocks) {
+            const uint32_t* r = rec + b * kLiveRec;
+            c = r[0];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) acc[k] += r[1 + k];
+            live += r[9];
+            if (r[7] != 0xFFFFFFFFu && first == ~0ull) first = b * kScrubSpan + r[7];
+            if (r[8]) last = b * kScrubSpan + r[8];  // a thread's spans ascend
+        }
+        uint64_t total;
+        const uint64_t before = block_excl_scan(c, w4, total);
+        if (b < nblocks) rank[b] = damaged + before;
+        damaged += total;
+        __syncthreads();
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const uint64_t v = wave_sum(acc[k]);
+        if ((threadIdx.x & 63) == 0 && v) atomicAdd(&tot[k], (unsigned long long)v);
+    }
+    live = wave_sum(live);
+    if ((threadIdx.x & 63) == 0 && live) atomicAdd(&tot[8], (unsigned long long)live);
+    if (first != ~0ull) atomicMin(&tot[6], (unsigned long long)first);
+    if (last) atomicMax(&tot[7], (unsigned long long)last);
+    __syncthreads();
+    if (threadIdx.x < kLiveSummaryWords) {
+        const int i = threadIdx.x;
+        const uint64_t n_live = tot[8];  // every owned page, whatever its class byte
+        uint64_t v = 0;
+        switch (i) {
+            case 0: v = n; break;
+            case 1: v = rows; break;
+            case 2: v = ctl[0]; break;
+            case 3: v = ctl[1]; break;
+            case 4: v = ctl[1] - n_live; break;  // rows that point into the window but own nothing
+            case 5: case 6: case 7: case 8: case 9: case 10: v = tot[i - 5]; break;
+            case 11: v = damaged; break;
+            case 12: v = tot[6]; break;
+            case 13: v = tot[7] ? tot[7] - 1 : ~0ull; break;
+            case 14: v = damaged < cap ? damaged : cap; break;
+            default: v = 0; break;
+        }
+        summary[i] = v;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_live_list(const uint8_t* __restrict__ cls, const uint32_t* __restrict__ owner,
+                                                  uint64_t n, const uint32_t* __restrict__ rec,
+                                                  const uint64_t* __restrict__ rank, uint64_t cap,
+                                                  uint64_t* __restrict__ list) {
+    __shared__ uint64_t w4[4];
+    const uint64_t r0 = rank[blockIdx.x];
+    if (rec[(uint64_t)blockIdx.x * kLiveRec] == 0 || r0 >= cap) return;  // uniform over the block
+    const uint64_t p0 = (uint64_t)blockIdx.x * kScrubSpan + threadIdx.x * 16u;
+    uint32_t mask = 0;
+    uint64_t cl = 0, ch = 0;
+    if (p0 < n) {
+        ld_bytes16(cls + p0, n - p0, 0xFF, cl, ch);
+        const int m = (int)min((uint64_t)16, n - p0);
+        for (int k = 0; k < m; ++k)
+            mask |= (owner[p0 + k] != 0xFFFFFFFFu && byte_of(cl, ch, k) != kClassOk ? 1u : 0u) << k;
+    }
+    uint64_t total;
+    uint64_t pos = r0 + block_excl_scan(__builtin_popcount(mask), w4, total);
+    while (mask && pos < cap) {
+        const int k = __builtin_ctz(mask);
+        mask &= mask - 1;
+        list[2 * pos] = p0 + k;  // pcs_live_page: index, then page_id | cls << 32
+        list[2 * pos + 1] = (uint64_t)owner[p0 + k] | (uint64_t)byte_of(cl, ch, k) << 32;
+        ++pos;
+    }
+}
+
+hipError_t run_scrub_live(const uint8_t* cls, uint64_t n, uint64_t fp_first, const uint64_t* table, uint64_t rows,
+                          uint32_t* owner, uint64_t* summary, uint64_t* list, uint64_t cap, hipStream_t s) {
+    const uint64_t nblocks = (n + kScrubSpan - 1) / kScrubSpan;
+    if (nblocks > 0x7FFFFFFFull || rows > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    ScratchLease scratch(s);  // counters, ranks, span records and (when the caller wants none) the owners
+    hipError_t e = scratch.get(4 * 8 + nblocks * 8 + nblocks * kLiveRec * 4 + (owner ? 0 : n * 4));
+    if (e != hipSuccess) return e;
+    uint64_t* ctl = static_cast<uint64_t*>(scratch.p);
+    uint64_t* rank = ctl + 4;
+    uint32_t* rec = reinterpret_cast<uint32_t*>(rank + nblocks);
+    if (!owner) owner = rec + nblocks * kLiveRec;
+    hipLaunchKernelGGL(k_live_fill, dim3(grid_for(n, kBlock, kBlocksPerCu)), dim3(kBlock), 0, s, n, owner, ctl);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (rows) {
+        hipLaunchKernelGGL(k_live_owner, dim3(grid_for(rows, kBlock, kBlocksPerCu)), dim3(kBlock), 0, s, table, rows,
+                           fp_first, n, owner, ctl);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    if (nblocks) {
+        hipLaunchKernelGGL(k_live_count, dim3((unsigned)nblocks), dim3(256), 0, s, cls, owner, n, rec);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_live_scan, dim3(1), dim3(256), 0, s, rec, nblocks, n, rows, cap, ctl, rank, summary);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (nblocks && cap) {
+        hipLaunchKernelGGL(k_live_list, dim3((unsigned)nblocks), dim3(256), 0, s, cls, owner, n, rec, rank, cap, list);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 hipError_t scratch_acquire(size_t bytes, void** out, int* id) { return g_scratch.acquire(bytes, out, id); }

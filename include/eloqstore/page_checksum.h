@@ -231,6 +231,63 @@ int TryScanManifests(std::span<const std::string_view> images, ManifestsReport& 
 ManifestsReport ScanManifests(std::span<const std::string_view> images, uint32_t align = 4096,
                               size_t max_records = 1 << 16);
 
+// Manifest replay (pcs_manifest_replay_host): what Replayer::Replay computes
+// (src/replayer.cpp:27-72, 142-228) for every image of a batch: the final
+// logical-page to file-page table, root, ttl_root and max_fp_id.  Manifest i's
+// rows are table[table_first .. table_first + table_size) when its status is
+// kOk; a row nobody wrote is MappingSnapshot::InvalidValue (7); a row maps file
+// page v >> 3 iff (v & 7) == 1.  max_rows caps the rows of the whole batch: a
+// manifest whose rows do not fit is kTableCap and writes none.
+enum class ReplayStatus : uint64_t { kOk = 0, kNotReplayable = 1, kMalformed = 2, kTableCap = 3 };
+struct ManifestReplay {
+    ReplayStatus status = ReplayStatus::kNotReplayable;
+    uint64_t n_replayed = 0;
+    uint64_t malformed_record = UINT64_MAX;  // lowest record that breaks a decode rule (kMalformed)
+    uint64_t root = 0, ttl_root = 0, max_fp_id = 0, dict_bytes = 0;
+    uint64_t snapshot_pages = 0, n_log_entries = 0;
+    uint64_t table_size = 0, table_first = 0;
+    uint64_t n_mapped = 0;
+    uint64_t min_fp = UINT64_MAX, max_fp = UINT64_MAX;  // of the mapped file page ids
+    uint64_t n_fp_beyond_max = 0;                       // mapped ids >= max_fp_id
+    uint64_t n_term_pairs = 0;
+};
+struct ManifestsReplay {
+    std::vector<ManifestReplay> manifests;
+    uint64_t n_by_status[4] = {};
+    uint64_t n_rows = 0, n_mapped = 0, n_log_entries = 0;
+    uint64_t first_bad_manifest = UINT64_MAX;  // first status other than kOk
+    std::vector<uint64_t> table;               // the n_rows_written rows of the kOk manifests, in order
+    std::vector<ManifestReport> scans;         // the scan's report of every image
+};
+// The call holds 8 bytes per row of max_rows on the host and 12 on the device
+// while it runs, whatever the manifests need: pass what the batch can hold.
+int TryReplayManifests(std::span<const std::string_view> images, ManifestsReplay& report, uint32_t align = 4096,
+                       size_t max_rows = 1 << 20);
+ManifestsReplay ReplayManifests(std::span<const std::string_view> images, uint32_t align = 4096,
+                                size_t max_rows = 1 << 20);
+
+// Scrub live (pcs_scrub_live_host): classes is a scrub's class byte per file
+// page fp_first .. fp_first + classes.size(), table a replayed mapping table.
+// A page is live iff a table row maps it; owner[i] is the lowest such row
+// (UINT32_MAX for a dead page).  damaged lists every live page whose class is
+// not ok, ascending, at most max_listed of them; n_damaged is always full.
+struct LivePage {
+    uint64_t index = 0;            // in the window
+    uint32_t page_id = 0, cls = 0; // its owner, its class byte
+};
+struct LiveReport {
+    uint64_t n_pages = 0, table_size = 0, n_mapped = 0, n_mapped_in_window = 0, n_duplicate = 0;
+    uint64_t live_ok = 0, live_blank = 0, live_corrupt = 0, dead_ok = 0, dead_blank = 0, dead_corrupt = 0;
+    uint64_t n_damaged = 0;
+    uint64_t first_damaged = UINT64_MAX, last_live = UINT64_MAX;
+    std::vector<LivePage> damaged;
+    std::vector<uint32_t> owner;
+};
+int TryScrubLive(std::span<const uint8_t> classes, uint64_t fp_first, std::span<const uint64_t> table,
+                 LiveReport& report, size_t max_listed = 1024);
+LiveReport ScrubLive(std::span<const uint8_t> classes, uint64_t fp_first, std::span<const uint64_t> table,
+                     size_t max_listed = 1024);
+
 // Registers a page-pool chunk or io_uring buffer ring once (PagesPool::Extend,
 // src/storage/page.cpp:95-120): batches whose pages all lie in registered
 // memory are then hashed in place over PCIe in one launch, with no gather

@@ -104,7 +104,11 @@ enum pcs_flags {
  *      pcs_pages_scrub_files_host, struct pcs_file_report and struct
  *      pcs_files_summary; pcs_manifest_scan_dev / pcs_manifest_scan_host, struct
  *      pcs_manifest_record, pcs_manifest_report and pcs_manifest_summary, and
- *      PCS_TUNE_MANIFEST_WALK_TILE */
+ *      PCS_TUNE_MANIFEST_WALK_TILE.  Added after 7 without a bump; detect with
+ *      dlsym: pcs_manifest_replay_dev / pcs_manifest_replay_host, enum
+ *      pcs_replay_status, struct pcs_replay_report and pcs_replay_summary;
+ *      pcs_scrub_live_dev / pcs_scrub_live_host, struct pcs_live_page and
+ *      pcs_live_summary; PCS_TUNE_REPLAY_TILE */
 #define PCS_ABI_VERSION 7
 int pcs_abi_version(void);
 const char *pcs_version(void);
@@ -576,6 +580,144 @@ int pcs_manifest_scan_host(const void *const *images, const uint64_t *sizes, uin
                            uint32_t align, pcs_manifest_report *reports, pcs_manifest_summary *summary,
                            pcs_manifest_record *records, uint64_t record_cap);
 
+/* ---- manifest replay: the mapping table a manifest describes ----------------
+ * What Replayer::Replay computes (src/replayer.cpp:27-72, 142-228, with
+ * ManifestBuilder's layout, src/storage/root_meta.cpp:29-105), for every image
+ * of a batch, on the device.  The call runs the scan above internally (its
+ * record scratch is sized by the scan's own bound, total_bytes / align +
+ * n_images; the caller passes no record array) and writes the scan's reports to
+ * d_scan_reports when that is given.
+ *
+ * Which records: verdict CLEAN or TORN_TAIL replays n_replayed = (first_corrupt
+ * == UINT64_MAX ? n_records : first_corrupt) records, record 0 as the snapshot
+ * and the others as logs; any other verdict is PCS_REPLAY_NOT_REPLAYABLE.  root
+ * and ttl_root are those of record n_replayed - 1.
+ *
+ * Varints (src/coding.cpp:141-201): little-endian base 128, a byte below 0x80
+ * ends one; a varint64 has at most 10 bytes and its value is the sum of
+ * (b_i & 0x7F) << 7i mod 2^64, a varint32 at most 5 bytes, value mod 2^32.
+ * Snapshot payload of L bytes: varint64 max_fp_id; varint32 dict_len (<= the
+ * bytes that remain, skipped); with rem bytes left, LE32 mapping_len with
+ * mapping_len + 8 <= rem; mapping_len bytes of varint64s, value j = table[j];
+ * LE32 term_len (<= the bytes after it); term_len bytes holding an even count
+ * of varint64s, only framed and counted; bytes after it are ignored.  Log
+ * payload: L >= 8, LE32 mapping_len with mapping_len + 8 <= L, the mapping
+ * section holds alternating varint32 page_id and varint64 value (whole varints,
+ * an even count), then the term section as in the snapshot.  A section must be
+ * a whole number of varints, none longer than its limit.  Where the reference
+ * asserts, CHECKs or LOG(FATAL)s on one of these, the image is
+ * PCS_REPLAY_MALFORMED with malformed_record the lowest record that breaks a
+ * rule; nothing outside the record is read and other images are unaffected.
+ *
+ * Apply: entries in record order, then byte order; a page's final value is that
+ * of its last entry.  table_size = max(snapshot count, 1 + largest page_id of a
+ * replayed log); a page nobody wrote is 7 (MappingSnapshot::InvalidValue).  A
+ * value maps a file page iff value & 7 == 1, its id is value >> 3.  max_fp_id =
+ * max(the snapshot's, id + 1 over EVERY replayed log entry that is a file page,
+ * overwritten ones included), as ReplayLog does.  n_term_pairs sums the term
+ * pairs of every replayed record.
+ *
+ * Rows: table_first is the exclusive sum of table_size over the images that are
+ * neither NOT_REPLAYABLE nor MALFORMED (for those two it is the running sum at
+ * that image, and every field but status, n_replayed, malformed_record and
+ * table_first is 0, min_fp / max_fp UINT64_MAX).  An image with table_first +
+ * table_size > table_cap gets PCS_REPLAY_TABLE_CAP: table_size, max_fp_id,
+ * root, ttl_root, dict_bytes, snapshot_pages, n_log_entries and n_term_pairs
+ * are still reported, it writes no rows and n_mapped, min_fp, max_fp and
+ * n_fp_beyond_max are 0, UINT64_MAX, UINT64_MAX and 0.  OK images write
+ * d_table[table_first + page_id]; rows of other images and everything at
+ * n_rows_written and beyond are not written.  d_table may be NULL iff table_cap
+ * == 0.  The output is identical from call to call: last-writer-wins is an
+ * atomicMax over a per-row sequence number, then the winner stores.
+ *
+ * The layout, alignment rules and limits are pcs_manifest_scan_dev's, plus
+ * total_bytes < 2^32 (PCS_ERR_INVALID otherwise).  The _dev form never
+ * synchronises; every grid and scratch size comes from the arguments alone
+ * (table_cap included: four bytes of scratch per row of d_table, so pass the
+ * table's real capacity); scratch is event-fenced per stream.  An invalid
+ * layout sets invalid_image, leaves every other summary word but n_images 0 and
+ * writes nothing else.  Sized for what a store holds (thousands of manifests of
+ * up to manifest_limit): the prelude pass runs one workgroup per image with a
+ * lane per record, and two exclusive sums, over 2 x records and over the decode
+ * tiles, run in one workgroup each, so a batch of millions of align-slots or one
+ * image of millions of records spends its time there on one CU; the record
+ * scratch is 72 bytes per align-slot of total_bytes.
+ *
+ * pcs_manifest_replay_host packs whole images into 32 MiB staging groups as
+ * pcs_manifest_scan_host does and carries table_first and the TABLE_CAP rule
+ * across the groups, so the result equals one call over the batch.
+ * PCS_TUNE_FAIL_INJECT applies to it. */
+enum pcs_replay_status {
+    PCS_REPLAY_OK = 0,
+    PCS_REPLAY_NOT_REPLAYABLE = 1, /* the scan's verdict is neither CLEAN nor TORN_TAIL */
+    PCS_REPLAY_MALFORMED = 2,      /* a replayed record breaks a decode rule */
+    PCS_REPLAY_TABLE_CAP = 3,      /* its rows do not fit below table_cap */
+};
+typedef struct pcs_replay_report { /* 16 x u64, one per image */
+    uint64_t status, n_replayed;
+    uint64_t malformed_record;     /* UINT64_MAX unless status is MALFORMED */
+    uint64_t root, ttl_root, max_fp_id, dict_bytes;
+    uint64_t snapshot_pages;       /* values in the snapshot's mapping section */
+    uint64_t n_log_entries;        /* (page_id, value) pairs of the replayed logs */
+    uint64_t table_size, table_first;
+    uint64_t n_mapped;             /* rows that map a file page */
+    uint64_t min_fp, max_fp;       /* smallest / largest mapped file page id, UINT64_MAX when n_mapped == 0 */
+    uint64_t n_fp_beyond_max;      /* mapped ids >= max_fp_id */
+    uint64_t n_term_pairs;
+} pcs_replay_report;
+typedef struct pcs_replay_summary { /* 12 x u64 */
+    uint64_t n_images, n_by_status[4];
+    uint64_t n_rows;               /* sum of table_size over OK and TABLE_CAP images */
+    uint64_t n_rows_written;       /* over OK images: rows [0, n_rows_written) of d_table */
+    uint64_t n_mapped, n_log_entries;
+    uint64_t first_bad_image;      /* first image whose status is not OK, UINT64_MAX when none */
+    uint64_t invalid_image;        /* UINT64_MAX when the layout is valid */
+    uint64_t reserved;             /* 0 */
+} pcs_replay_summary;
+int pcs_manifest_replay_dev(const void *d_base, uint64_t total_bytes, const uint64_t *d_img_off,
+                            const uint64_t *d_img_size, uint64_t n_images, uint32_t align,
+                            pcs_manifest_report *d_scan_reports /* may be NULL */, pcs_replay_report *d_reports,
+                            pcs_replay_summary *d_summary, uint64_t *d_table, uint64_t table_cap,
+                            pcs_stream_t stream);
+int pcs_manifest_replay_host(const void *const *images, const uint64_t *sizes, uint64_t n_images, uint32_t align,
+                             pcs_manifest_report *scan_reports /* may be NULL */, pcs_replay_report *reports,
+                             pcs_replay_summary *summary, uint64_t *table, uint64_t table_cap);
+
+/* ---- scrub live: which damaged pages the tree still points to ---------------
+ * In append mode a data file is mostly superseded copies: a corrupt dead page
+ * is harmless, a blank or corrupt MAPPED page is data loss.  d_class is a
+ * scrub's class bytes for file pages fp_first .. fp_first + n_pages, d_table a
+ * replayed mapping table of table_size rows (<= 2^32 - 1).  Page i is live iff
+ * some table[p] == ((fp_first + i) << 3 | 1); d_owner[i] is the lowest such p,
+ * else UINT32_MAX (d_owner may be NULL: scratch is used).  n_mapped counts the
+ * mapped rows of the whole table, n_mapped_in_window those that point into the
+ * window, n_duplicate those of them that are not the owner.  The six cells
+ * count class bytes 0, 1 and 2 only; d_damaged lists every live page whose
+ * class byte is not PCS_PAGE_OK, ascending by index with page_id its owner,
+ * capped at damaged_cap (n_damaged is always full; the same from call to
+ * call).  d_damaged may be NULL iff damaged_cap == 0; table_size == 0 and
+ * n_pages == 0 are legal.  The _dev form never synchronises; the _host form
+ * copies the class bytes and the table to the device and runs it. */
+typedef struct pcs_live_page {
+    uint64_t index;        /* page index in the window */
+    uint32_t page_id, cls; /* its owner and its class byte */
+} pcs_live_page;
+typedef struct pcs_live_summary { /* 16 x u64 */
+    uint64_t n_pages, table_size, n_mapped, n_mapped_in_window, n_duplicate;
+    uint64_t live_ok, live_blank, live_corrupt, dead_ok, dead_blank, dead_corrupt;
+    uint64_t n_damaged;
+    uint64_t first_damaged; /* UINT64_MAX when none */
+    uint64_t last_live;     /* UINT64_MAX when no page is live */
+    uint64_t n_listed;      /* min(n_damaged, damaged_cap) */
+    uint64_t reserved;      /* 0 */
+} pcs_live_summary;
+int pcs_scrub_live_dev(const uint8_t *d_class, uint64_t n_pages, uint64_t fp_first, const uint64_t *d_table,
+                       uint64_t table_size, uint32_t *d_owner /* may be NULL */, pcs_live_summary *d_summary,
+                       pcs_live_page *d_damaged, uint64_t damaged_cap, pcs_stream_t stream);
+int pcs_scrub_live_host(const uint8_t *cls, uint64_t n_pages, uint64_t fp_first, const uint64_t *table,
+                        uint64_t table_size, uint32_t *owner /* may be NULL */, pcs_live_summary *summary,
+                        pcs_live_page *damaged, uint64_t damaged_cap);
+
 /* ---- sharding ------------------------------------------------------------
  * Contiguous page range [begin, end) of rank `rank` of `world` for n pages:
  * begin = floor(rank * n / world).  Pages are independent, so G GPUs hash G
@@ -686,6 +828,11 @@ int pcs_shard_range(uint64_t n, int world, int rank, uint64_t *begin, uint64_t *
  *                                     of the chain walk, a power of two in
  *                                     [64, 4096] (any other value runs at the
  *                                     default); results do not depend on it
+ *   PCS_TUNE_REPLAY_TILE        [4096] manifest replay: bytes of a mapping
+ *                                     section per decode work item (one wave),
+ *                                     a power of two in [64, 4096]; setting any
+ *                                     other value fails; results do not depend
+ *                                     on it (sweep: profiles/replay/replay_rate.txt)
  * Keys 4, 5, 10, 12, 14, 16-22, 25, 29 and 32 selected variants that measured slower or no
  * better (XXH64 quad nt loads, in-place stamp widths, descriptor tile sorts,
  * 4 KiB slices, wave-dealt pages and slice streams, pipelined split-page
@@ -718,6 +865,7 @@ enum pcs_tune_key {
     PCS_TUNE_SYNC_SPIN_US = 35,
     PCS_TUNE_SERVICE_DEPARTURE = 36,
     PCS_TUNE_MANIFEST_WALK_TILE = 38, /* 37 was never assigned and stays unknown */
+    PCS_TUNE_REPLAY_TILE = 39,
 };
 int pcs_set_tuning(int key, int64_t value);
 int64_t pcs_get_tuning(int key); /* -1 for an unknown key */

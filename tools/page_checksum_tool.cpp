@@ -48,6 +48,18 @@
 //       valid_prefix_bytes); exit 2 if any manifest is broken or has a bad
 //       snapshot, else 3 if any has a torn tail, else 1 if any is empty or
 //       unreadable, else 0.
+//   page_checksum_tool --live <manifest> <page_size> <pages_per_file_shift> <data_file>...
+//       is any page the tree still points to damaged?  The manifest is replayed
+//       (pcs_manifest_replay_host); when it cannot be (not replayable or
+//       malformed) one line says why, exit 2.  A data file's id comes from its
+//       base name data_<file_id>_<term> (a name that does not parse: exit 1);
+//       each file is scrubbed (pcs_pages_scrub_host) and its class bytes go to
+//       pcs_scrub_live_host with fp_first = file_id << shift.  One line per
+//       file with live ok/blank/corrupt and dead ok/blank/corrupt, one line per
+//       damaged live page (page id, file page id, class), then root, ttl_root,
+//       max_fp_id, the mapped pages and how many of them lie in files not
+//       given.  Exit 2 if any live page is corrupt, else 3 if any is blank,
+//       else 0; dead damage never fails the run.
 //   --scan/--stamp print a summary line with the GiB/s of the call; exit codes
 //   as above (--scan: 2 if any page is corrupted).
 #include <fcntl.h>
@@ -69,6 +81,7 @@
 #include "eloqstore_pcs.h"
 #include "extent_merge.h"
 #include "file_merge.h"
+#include "manifest_replay.h"
 #include "manifest_scan.h"
 #include "scrub_merge.h"
 
@@ -100,8 +113,11 @@ void usage(const char* prog) {
                  "       %s --gen <file_path> <n_pages> [page_size_bytes] [seed]\n"
                  "       %s --check-manifest <manifest_file>...\n"
                  "           one file: the manifest_check_tool report (exit 2: a checksum failed);\n"
-                 "           several: a line per file (exit 2: broken or bad snapshot, 3: torn tail, 1: empty)\n",
-                 prog, prog, prog, prog, prog, prog, prog);
+                 "           several: a line per file (exit 2: broken or bad snapshot, 3: torn tail, 1: empty)\n"
+                 "       %s --live <manifest_file> <page_size_bytes> <pages_per_file_shift> <data_file>...\n"
+                 "           exit 2: a mapped page is corrupt or the manifest cannot be replayed; exit 3: a mapped\n"
+                 "           page is blank; damage in pages the manifest no longer maps never fails the run\n",
+                 prog, prog, prog, prog, prog, prog, prog, prog);
 }
 
 constexpr uint64_t kDefaultPageSize = 4096;  // KvOptions{}.data_page_size
@@ -691,7 +707,109 @@ int check_manifests(int n_paths, char** paths) {
     return pcs::manifest_tool_exit(reports.data(), n, unreadable);
 }
 
+static bool read_whole(const char* path, std::vector<char>& bytes) {
+    FILE* f = std::fopen(path, "rb");
+    if (!f) {
+        std::fprintf(stderr, "Failed to open %s: %s\n", path, std::strerror(errno));
+        return false;
+    }
+    char chunk[1 << 16];
+    size_t got;
+    while ((got = std::fread(chunk, 1, sizeof chunk, f)) > 0) bytes.insert(bytes.end(), chunk, chunk + got);
+    std::fclose(f);
+    return true;
+}
+
+// --live: replay the manifest, scrub every data file, and ask of each file's
+// class bytes which pages the replayed table still points to.
+int live(const char* manifest, const char* size_s, const char* shift_s, int n_files, char** files) {
+    constexpr uint32_t kPageAlign = 4096;
+    uint64_t page_size = 0, shift = 0;
+    if (!parse_u64(size_s, page_size) || page_size == 0 || !parse_u64(shift_s, shift) || shift > 40) {
+        std::fprintf(stderr, "Invalid page size or pages_per_file_shift\n");
+        return 1;
+    }
+    std::vector<uint64_t> ids(n_files);
+    for (int f = 0; f < n_files; ++f) {
+        uint64_t term = 0;
+        if (!pcs::live_parse_data_file(files[f], ids[f], term)) {
+            std::fprintf(stderr, "Not a data file name (data_<file_id>_<term>): %s\n", files[f]);
+            return 1;
+        }
+        for (int g = 0; g < f; ++g) {
+            if (ids[g] == ids[f]) {  // its mapped pages would be counted twice
+                std::fprintf(stderr, "File id %llu is given twice: %s\n", (unsigned long long)ids[f], files[f]);
+                return 1;
+            }
+        }
+    }
+    std::vector<char> image;
+    if (!read_whole(manifest, image)) return 1;
+    const void* ptr = image.data();
+    const uint64_t size = image.size();
+    pcs_replay_report rep{};
+    pcs_replay_summary sum{};
+    // the rows are not known before the replay: ask without a table first
+    if (const int rc = pcs_manifest_replay_host(&ptr, &size, 1, kPageAlign, nullptr, &rep, &sum, nullptr, 0)) {
+        std::fprintf(stderr, "Manifest replay failed (%d): %s\n", rc, pcs_last_error());
+        return 1;
+    }
+    std::vector<uint64_t> table(rep.status == PCS_REPLAY_TABLE_CAP ? rep.table_size : 0);
+    if (!table.empty()) {
+        if (const int rc = pcs_manifest_replay_host(&ptr, &size, 1, kPageAlign, nullptr, &rep, &sum, table.data(),
+                                                    table.size())) {
+            std::fprintf(stderr, "Manifest replay failed (%d): %s\n", rc, pcs_last_error());
+            return 1;
+        }
+    }
+    const std::string refusal = pcs::live_tool_refusal(manifest, rep);
+    if (!refusal.empty()) {
+        std::fputs(refusal.c_str(), stdout);
+        return 2;
+    }
+    std::vector<pcs_live_summary> sums;
+    uint64_t mapped_in_files = 0;
+    for (int f = 0; f < n_files; ++f) {
+        std::vector<char> bytes;
+        if (!read_whole(files[f], bytes)) return 1;
+        const uint64_t n_pages = bytes.size() / page_size;
+        if (n_pages > (1ull << shift)) {
+            std::fprintf(stderr, "%s holds more than 1 << %llu pages\n", files[f], (unsigned long long)shift);
+            return 1;
+        }
+        std::vector<const void*> pages(n_pages);
+        for (uint64_t p = 0; p < n_pages; ++p) pages[p] = bytes.data() + p * page_size;
+        std::vector<uint8_t> cls(n_pages);
+        pcs_scrub_summary ssum{};
+        if (const int rc = pcs_pages_scrub_host(pages.data(), page_size, n_pages, cls.data(), nullptr, &ssum, nullptr, 0)) {
+            std::fprintf(stderr, "Scrub of %s failed (%d): %s\n", files[f], rc, pcs_last_error());
+            return 1;
+        }
+        const uint64_t fp_first = ids[f] << shift;
+        pcs_live_summary ls{};
+        std::vector<pcs_live_page> damaged(n_pages);
+        if (const int rc = pcs_scrub_live_host(cls.data(), n_pages, fp_first, table.data(), table.size(), nullptr, &ls,
+                                               damaged.data(), damaged.size())) {
+            std::fprintf(stderr, "Scrub live of %s failed (%d): %s\n", files[f], rc, pcs_last_error());
+            return 1;
+        }
+        std::fputs(pcs::live_tool_file_line(files[f], ids[f], ls).c_str(), stdout);
+        for (uint64_t k = 0; k < ls.n_listed; ++k) std::fputs(pcs::live_tool_page_line(fp_first, damaged[k]).c_str(), stdout);
+        mapped_in_files += ls.n_mapped_in_window;
+        sums.push_back(ls);
+    }
+    std::fputs(pcs::live_tool_footer(rep, mapped_in_files).c_str(), stdout);
+    return pcs::live_tool_exit(sums.data(), sums.size());
+}
+
 int main(int argc, char** argv) {
+    if (argc >= 2 && !std::strcmp(argv[1], "--live")) {
+        if (argc < 6) {
+            usage(argv[0]);
+            return 1;
+        }
+        return live(argv[2], argv[3], argv[4], argc - 5, argv + 5);
+    }
     if (argc >= 2 && !std::strcmp(argv[1], "--check-manifest")) {
         if (argc < 3) {
             usage(argv[0]);
