@@ -87,6 +87,8 @@ _SIGS = {
     "pcs_manifest_replay_host": [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp, _u64],
     "pcs_scrub_live_dev": [_vp, _u64, _u64, _vp, _u64, _vp, _vp, _vp, _u64, _vp],
     "pcs_scrub_live_host": [_vp, _u64, _u64, _vp, _u64, _vp, _vp, _vp, _u64],
+    "pcs_tree_check_dev": [_vp, _u64, _u64, _u64, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _u64, _vp],
+    "pcs_tree_check_host": [_vp, _u64, _u64, _u64, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _u64],
     "pcs_set_tuning": [_i32, ctypes.c_int64],
     "pcs_get_tuning": [_i32],
     "pcs_counter": [_i32],
@@ -708,6 +710,105 @@ def scrub_live_host(cls, fp_first: int, table, damaged_cap: int = 1024, want_own
           table.size, owner.ctypes.data if want_owner else 0, summary.ctypes.data,
           damaged.ctypes.data if damaged_cap else 0, damaged_cap)
     return (owner[:n] if want_owner else None), summary[0], damaged[: int(summary[0]["n_listed"])]
+
+
+# pcs_tree_node (16 bytes), pcs_tree_problem (16 bytes), pcs_tree_summary (32 u64 words)
+TREE_NODE_DTYPE = np.dtype([("parent", "<u4"), ("depth", "u1"), ("tree", "u1"), ("type", "u1"), ("bits", "u1"),
+                            ("n_children", "<u4"), ("n_bad_children", "<u4")])
+TREE_PROBLEM_DTYPE = np.dtype([("page_id", "<u4"), ("parent", "<u4"), ("bits", "<u4"), ("depth", "<u4")])
+TREE_SUMMARY_DTYPE = np.dtype([
+    ("n_pages", "<u8"), ("table_size", "<u8"), ("n_mapped", "<u8"), ("n_reached", "<u8"), ("n_nonleaf", "<u8"),
+    ("n_leaf_index", "<u8"), ("n_data", "<u8"), ("n_refs", "<u8"), ("n_extra_refs", "<u8"),
+    ("n_out_of_range_refs", "<u8"), ("max_depth", "<u8"), ("n_depth_capped", "<u8"), ("n_by_bit", "<u8", (8,)),
+    ("n_problems", "<u8"), ("first_problem", "<u8"), ("n_listed", "<u8"), ("n_unreached_mapped", "<u8"),
+    ("unreached_by_type", "<u8", (6,)), ("n_unreached_unread", "<u8"), ("n_chain_heads", "<u8")])
+(TREE_UNMAPPED, TREE_ABSENT, TREE_BLANK, TREE_CORRUPT, TREE_WRONG_TYPE, TREE_MALFORMED, TREE_BAD_CHILD,
+ TREE_BAD_LINK) = (1 << k for k in range(8))
+TREE_MAX_DEPTH = 16
+TREE_CLASS_ABSENT = 3  # the class byte of a page that was not loaded
+
+
+def tree_check_async(pages, page_size: int, n_pages: int, fp_first: int, cls, table, roots, n_roots: int = 2,
+                     table_size: int | None = None, nodes=None, summary=None, problems=None, problem_cap: int = 1024,
+                     stream=None):
+    """pcs_tree_check_dev, enqueue only: pages and cls are the device bytes of
+    the window's file pages and their scrub classes, table a device int64
+    mapping table (None with table_size 0), roots a device int64 tensor or a
+    device ADDRESS (for instance that of a replay report's root word) of
+    n_roots words; returns the device tensors (nodes table_size x 2 int64 words,
+    or None when nodes is False; the 32 summary words; the problems as
+    problem_cap x 2 int64 words), valid once the stream is synchronised."""
+    device = summary.device if summary is not None else cls.device if cls is not None else table.device
+    if table_size is None:
+        table_size = 0 if table is None else table.numel()
+    if nodes is None:
+        nodes = torch.empty((max(table_size, 1), 2), dtype=torch.int64, device=device)
+    if summary is None:
+        summary = torch.empty(32, dtype=torch.int64, device=device)
+    if problems is None and problem_cap:
+        problems = torch.empty((problem_cap, 2), dtype=torch.int64, device=device)
+    _call("pcs_tree_check_dev", _ptr(pages) if n_pages else 0, page_size, n_pages, fp_first,
+          _ptr(cls) if n_pages else 0, _ptr(table) if table_size else 0, table_size, _ptr(roots), n_roots,
+          _ptr(None if nodes is False else nodes), _ptr(summary), _ptr(problems) if problem_cap else 0, problem_cap,
+          _stream(stream))
+    return (None if nodes is False else nodes), summary, problems
+
+
+def _tree_roots(roots, device):
+    if isinstance(roots, (torch.Tensor, int)):
+        return roots, None
+    r = np.ascontiguousarray(roots, dtype=np.uint64)
+    return torch.from_numpy(r.view(np.int64).copy()).to(device), r.size
+
+
+def tree_check(pages, page_size: int, n_pages: int, fp_first: int, cls, table, roots, n_roots: int | None = None,
+               nodes=None, problem_cap: int = 1024, stream=None):
+    """Walk the index tree from `roots` over device pages -> (nodes
+    (TREE_NODE_DTYPE, one per table row; None when nodes is False), summary
+    (one TREE_SUMMARY_DTYPE record), the n_listed problems
+    (TREE_PROBLEM_DTYPE)).  table and roots may be device tensors or host
+    arrays.  Waits for the stream."""
+    device = pages.device
+    if table is not None and not isinstance(table, torch.Tensor):
+        table = torch.from_numpy(np.ascontiguousarray(table, dtype=np.uint64).view(np.int64).copy()).to(device)
+    roots, n = _tree_roots(roots, device)
+    if n_roots is None:
+        n_roots = n if n is not None else roots.numel() if isinstance(roots, torch.Tensor) else 2
+    table_size = 0 if table is None else table.numel()
+    nodes, summary, problems = tree_check_async(pages, page_size, n_pages, fp_first, cls, table, roots, n_roots,
+                                                table_size, nodes, None, None, problem_cap, stream)
+    if stream is not None:
+        _call("pcs_synchronize", _stream(stream))
+    s = np.ascontiguousarray(summary.cpu().numpy()).view(np.uint64).view(TREE_SUMMARY_DTYPE)[0]
+    listed = int(s["n_listed"])
+    probs = (np.ascontiguousarray(problems[:listed].cpu().numpy()).view(np.uint8).view(TREE_PROBLEM_DTYPE).reshape(-1)
+             if listed else np.zeros(0, dtype=TREE_PROBLEM_DTYPE))
+    nd = None
+    if nodes is not None:
+        nd = (np.ascontiguousarray(nodes[:table_size].cpu().numpy()).view(np.uint8).view(TREE_NODE_DTYPE).reshape(-1)
+              if table_size else np.zeros(0, dtype=TREE_NODE_DTYPE))
+    return nd, s, probs
+
+
+def tree_check_host(pages, page_size: int, fp_first: int, cls, table, roots, problem_cap: int = 1024,
+                    want_nodes: bool = True):
+    """pcs_tree_check_host over host arrays (pages one contiguous uint8 buffer;
+    cls None scrubs the pages on the device) -> (nodes, summary, problems) as
+    tree_check."""
+    pages = np.ascontiguousarray(pages, dtype=np.uint8).reshape(-1)
+    n = pages.size // page_size
+    if cls is not None:
+        cls = np.ascontiguousarray(cls, dtype=np.uint8)
+    table = np.ascontiguousarray(table, dtype=np.uint64)
+    roots = np.ascontiguousarray(roots, dtype=np.uint64)
+    nodes = np.zeros(max(1, table.size), dtype=TREE_NODE_DTYPE)
+    summary = np.zeros(1, dtype=TREE_SUMMARY_DTYPE)
+    problems = np.zeros(max(1, problem_cap), dtype=TREE_PROBLEM_DTYPE)
+    _call("pcs_tree_check_host", pages.ctypes.data if n else 0, page_size, n, fp_first,
+          cls.ctypes.data if cls is not None and n else 0, table.ctypes.data if table.size else 0, table.size,
+          roots.ctypes.data, roots.size, nodes.ctypes.data if want_nodes else 0, summary.ctypes.data,
+          problems.ctypes.data if problem_cap else 0, problem_cap)
+    return (nodes[: table.size] if want_nodes else None), summary[0], problems[: int(summary[0]["n_listed"])]
 
 
 class Batch:

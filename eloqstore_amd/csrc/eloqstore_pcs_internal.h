@@ -98,6 +98,16 @@ hipError_t run_manifest_replay(const uint8_t* base, uint64_t total, const uint64
 // ascending.  All device memory; enqueues on s and never waits.
 hipError_t run_scrub_live(const uint8_t* cls, uint64_t n, uint64_t fp_first, const uint64_t* table, uint64_t rows,
                           uint32_t* owner, uint64_t* summary, uint64_t* list, uint64_t cap, hipStream_t s);
+// Tree check (tree_check.hip) of the file pages [fp_first, fp_first + n) of
+// page_size bytes each (32 .. 65535) with class bytes cls[0 .. n), against the
+// mapping table table[0 .. rows) (rows < 2^32) from the n_roots (1 .. 8) device
+// words roots: nodes = 2 words per row (pcs_tree_node; may be null: scratch is
+// leased), summary = the 32 words of pcs_tree_summary, list[0 ..
+// min(n_problems, cap)) = pcs_tree_problem, ascending.  All device memory;
+// enqueues on s and never waits.
+hipError_t run_tree_check(const uint8_t* pages, uint64_t page_size, uint64_t n, uint64_t fp_first, const uint8_t* cls,
+                          const uint64_t* table, uint64_t rows, const uint64_t* roots, uint32_t n_roots,
+                          uint64_t* nodes, uint64_t* summary, uint64_t* list, uint64_t cap, hipStream_t s);
 // Event-fenced device scratch (see ScratchPool in pcs_kernels.hip): the
 // buffer is reused only after the work queued on `s` at release completes.
 hipError_t scratch_acquire(size_t bytes, void** out, int* id);

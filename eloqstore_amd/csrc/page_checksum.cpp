@@ -345,6 +345,55 @@ LiveReport ScrubLive(std::span<const uint8_t> classes, uint64_t fp_first, std::s
     return report;
 }
 
+int TryCheckTree(std::span<const uint8_t> pages, size_t page_size, uint64_t fp_first,
+                 std::span<const uint8_t> classes, std::span<const uint64_t> table, std::span<const uint64_t> roots,
+                 TreeReport& report, size_t max_listed) {
+    static_assert(sizeof(TreeNode) == sizeof(pcs_tree_node), "TreeNode mirrors pcs_tree_node");
+    static_assert(sizeof(TreeProblem) == sizeof(pcs_tree_problem), "TreeProblem mirrors pcs_tree_problem");
+    if (page_size == 0 || pages.size() % page_size) return PCS_ERR_INVALID;
+    const uint64_t n_pages = pages.size() / page_size;
+    if (!classes.empty() && classes.size() != n_pages) return PCS_ERR_INVALID;
+    report.nodes.assign(table.size(), TreeNode{});
+    report.problems.assign(max_listed, TreeProblem{});
+    pcs_tree_summary sum{};
+    const int rc = pcs_tree_check_host(pages.data(), page_size, n_pages, fp_first,
+                                       classes.empty() ? nullptr : classes.data(), table.data(), table.size(),
+                                       roots.data(), static_cast<uint32_t>(std::min<size_t>(roots.size(), UINT32_MAX)),
+                                       reinterpret_cast<pcs_tree_node*>(report.nodes.data()), &sum,
+                                       reinterpret_cast<pcs_tree_problem*>(report.problems.data()), max_listed);
+    if (rc != PCS_OK) return rc;
+    report.n_pages = sum.n_pages;
+    report.table_size = sum.table_size;
+    report.n_mapped = sum.n_mapped;
+    report.n_reached = sum.n_reached;
+    report.n_nonleaf = sum.n_nonleaf;
+    report.n_leaf_index = sum.n_leaf_index;
+    report.n_data = sum.n_data;
+    report.n_refs = sum.n_refs;
+    report.n_extra_refs = sum.n_extra_refs;
+    report.n_out_of_range_refs = sum.n_out_of_range_refs;
+    report.max_depth = sum.max_depth;
+    report.n_depth_capped = sum.n_depth_capped;
+    for (int k = 0; k < 8; ++k) report.n_by_bit[k] = sum.n_by_bit[k];
+    report.n_problems = sum.n_problems;
+    report.first_problem = sum.first_problem;
+    report.n_unreached_mapped = sum.n_unreached_mapped;
+    for (int k = 0; k < 6; ++k) report.unreached_by_type[k] = sum.unreached_by_type[k];
+    report.n_unreached_unread = sum.n_unreached_unread;
+    report.n_chain_heads = sum.n_chain_heads;
+    report.problems.resize(sum.n_listed);
+    return PCS_OK;
+}
+
+TreeReport CheckTree(std::span<const uint8_t> pages, size_t page_size, uint64_t fp_first,
+                     std::span<const uint8_t> classes, std::span<const uint64_t> table,
+                     std::span<const uint64_t> roots, size_t max_listed) {
+    TreeReport report;
+    if (int rc = TryCheckTree(pages, page_size, fp_first, classes, table, roots, report, max_listed))
+        die("CheckTree", rc);
+    return report;
+}
+
 void RegisterPagePool(void* base, size_t bytes) {
     if (int rc = pcs_host_register(base, bytes)) die("RegisterPagePool", rc);
 }

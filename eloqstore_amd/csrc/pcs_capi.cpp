@@ -12,6 +12,7 @@
 #include "manifest_replay.h"
 #include "manifest_scan.h"
 #include "scrub_merge.h"
+#include "tree_check.h"
 
 #include <hip/hip_runtime.h>
 
@@ -1663,6 +1664,64 @@ int host_scrub_live(const uint8_t* cls, uint64_t n_pages, uint64_t fp_first, con
     return finish(e, "scrub live");
 }
 
+// pcs_tree_check_host: the whole window goes to the device with one plain copy
+// (no staging ring: the walk needs every page resident at once), is scrubbed
+// there when the caller gives no class bytes, and the _dev form runs.
+int host_tree_check(const void* pages, uint64_t page_size, uint64_t n_pages, uint64_t fp_first, const uint8_t* cls,
+                    const uint64_t* table, uint64_t table_size, const uint64_t* roots, uint32_t n_roots,
+                    pcs_tree_node* nodes, pcs_tree_summary* summary, pcs_tree_problem* problems, uint64_t problem_cap) {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return hip_fail(e, "hipGetDevice");
+    Slot& slot = t_ctx[dev].slot[0];
+    if (int rc = ensure_slot(slot, 1, 1)) return rc;
+    hipStream_t s = slot.stream;
+    const uint64_t cap = std::min(problem_cap, table_size);  // no more problems than rows
+    const uint64_t page_bytes = (n_pages * page_size + 15) & ~uint64_t(15), cls_bytes = (n_pages + 7) & ~uint64_t(7);
+    void* buf = nullptr;
+    int id = -1;
+    e = pcs::scratch_acquire(page_bytes + sizeof(pcs_tree_summary) + sizeof(pcs_scrub_summary) + 8 * 8 +
+                                 table_size * 8 + (nodes ? table_size * sizeof(pcs_tree_node) : 0) +
+                                 cap * sizeof(pcs_tree_problem) + cls_bytes + 16,
+                             &buf, &id);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(PCS_ERR_NOMEM, "the window does not fit in device memory");
+    }
+    uint8_t* d_pages = static_cast<uint8_t*>(buf);
+    pcs_tree_summary* d_sum = reinterpret_cast<pcs_tree_summary*>(d_pages + page_bytes);
+    pcs_scrub_summary* d_ssum = reinterpret_cast<pcs_scrub_summary*>(d_sum + 1);
+    uint64_t* d_roots = reinterpret_cast<uint64_t*>(d_ssum + 1);
+    uint64_t* d_table = d_roots + 8;
+    pcs_tree_node* d_nodes = reinterpret_cast<pcs_tree_node*>(d_table + table_size);
+    pcs_tree_problem* d_list = reinterpret_cast<pcs_tree_problem*>(d_nodes + (nodes ? table_size : 0));
+    uint8_t* d_cls = reinterpret_cast<uint8_t*>(d_list + cap);
+    if (n_pages) e = hipMemcpyAsync(d_pages, pages, n_pages * page_size, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && n_pages && cls) e = hipMemcpyAsync(d_cls, cls, n_pages, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && n_pages && !cls)
+        e = pcs::run_scrub(d_pages, page_size, n_pages, d_cls, nullptr, reinterpret_cast<uint64_t*>(d_ssum), nullptr, 0,
+                           s);
+    if (e == hipSuccess && table_size) e = hipMemcpyAsync(d_table, table, table_size * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_roots, roots, n_roots * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = pcs::run_tree_check(d_pages, page_size, n_pages, fp_first, d_cls, d_table, table_size, d_roots, n_roots,
+                                nodes ? reinterpret_cast<uint64_t*>(d_nodes) : nullptr,
+                                reinterpret_cast<uint64_t*>(d_sum), reinterpret_cast<uint64_t*>(cap ? d_list : nullptr),
+                                cap, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(summary, d_sum, sizeof(*summary), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && nodes && table_size)
+        e = hipMemcpyAsync(nodes, d_nodes, table_size * sizeof(pcs_tree_node), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess && summary->n_listed) {
+        e = hipMemcpyAsync(problems, d_list, summary->n_listed * sizeof(pcs_tree_problem), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+    }
+    (void)pcs::scratch_release(id, s);
+    if (e != hipSuccess) (void)hipStreamSynchronize(s);  // nothing of this call left in flight
+    if (e == hipSuccess) summary->n_listed = std::min(summary->n_problems, problem_cap);
+    return finish(e, "tree check");
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -2552,6 +2611,44 @@ int pcs_scrub_live_host(const uint8_t* cls, uint64_t n_pages, uint64_t fp_first,
     if (injected_failure()) return fail(PCS_ERR_HIP, "injected failure (PCS_TUNE_FAIL_INJECT)");
     if (int rc = require_device()) return rc;
     return host_scrub_live(cls, n_pages, fp_first, table, table_size, owner, summary, damaged, damaged_cap);
+}
+
+int pcs_tree_check_dev(const void* d_pages, uint64_t page_size, uint64_t n_pages, uint64_t fp_first,
+                       const uint8_t* d_class, const uint64_t* d_table, uint64_t table_size, const uint64_t* d_roots,
+                       uint32_t n_roots, pcs_tree_node* d_nodes, pcs_tree_summary* d_summary,
+                       pcs_tree_problem* d_problems, uint64_t problem_cap, pcs_stream_t stream) {
+    static_assert(sizeof(pcs_tree_node) == 16, "pcs_tree_node is 16 bytes");
+    static_assert(sizeof(pcs_tree_problem) == 16, "pcs_tree_problem is 16 bytes");
+    static_assert(sizeof(pcs_tree_summary) == 32 * sizeof(uint64_t), "pcs_tree_summary is 32 x u64");
+    if (const char* why = pcs::tree_args(d_pages, page_size, n_pages, fp_first, d_table, table_size, d_roots, n_roots,
+                                         d_summary, d_problems, problem_cap))
+        return fail(PCS_ERR_INVALID, why);
+    if (n_pages && !d_class) return fail(PCS_ERR_INVALID, "class bytes are null");
+    if (reinterpret_cast<uintptr_t>(d_table) % 8 || reinterpret_cast<uintptr_t>(d_roots) % 8 ||
+        reinterpret_cast<uintptr_t>(d_nodes) % 8 || reinterpret_cast<uintptr_t>(d_summary) % 8 ||
+        reinterpret_cast<uintptr_t>(d_problems) % 8)
+        return fail(PCS_ERR_INVALID, "d_table, d_roots, d_nodes, d_summary or d_problems is misaligned");
+    if (int rc = require_device()) return rc;
+    return finish(pcs::run_tree_check(static_cast<const uint8_t*>(d_pages), page_size, n_pages, fp_first, d_class,
+                                      d_table, table_size, d_roots, n_roots, reinterpret_cast<uint64_t*>(d_nodes),
+                                      reinterpret_cast<uint64_t*>(d_summary), reinterpret_cast<uint64_t*>(d_problems),
+                                      problem_cap, reinterpret_cast<hipStream_t>(stream)),
+                  "tree check kernel launch");
+}
+
+int pcs_tree_check_host(const void* pages, uint64_t page_size, uint64_t n_pages, uint64_t fp_first, const uint8_t* cls,
+                        const uint64_t* table, uint64_t table_size, const uint64_t* roots, uint32_t n_roots,
+                        pcs_tree_node* nodes, pcs_tree_summary* summary, pcs_tree_problem* problems,
+                        uint64_t problem_cap) {
+    if (const char* why = pcs::tree_args(pages, page_size, n_pages, fp_first, table, table_size, roots, n_roots,
+                                         summary, problems, problem_cap))
+        return fail(PCS_ERR_INVALID, why);
+    if (!cls && n_pages && page_size < 249)
+        return fail(PCS_ERR_INVALID, "page_size must be >= 249 to scrub the pages (cls is null)");
+    if (injected_failure()) return fail(PCS_ERR_HIP, "injected failure (PCS_TUNE_FAIL_INJECT)");
+    if (int rc = require_device()) return rc;
+    return host_tree_check(pages, page_size, n_pages, fp_first, cls, table, table_size, roots, n_roots, nodes, summary,
+                           problems, problem_cap);
 }
 
 int pcs_shard_range(uint64_t n, int world, int rank, uint64_t* begin, uint64_t* end) {

@@ -288,6 +288,42 @@ int TryScrubLive(std::span<const uint8_t> classes, uint64_t fp_first, std::span<
 LiveReport ScrubLive(std::span<const uint8_t> classes, uint64_t fp_first, std::span<const uint64_t> table,
                      size_t max_listed = 1024);
 
+// Tree check (pcs_tree_check_host): walks the index tree that hangs off every
+// root of a replayed table, breadth-first, over the file pages fp_first ..
+// fp_first + pages.size() / page_size held in ONE contiguous buffer (the whole
+// window must fit in device memory).  classes are a scrub's class bytes for
+// those pages; an empty span scrubs them on the device first.  A root >=
+// UINT32_MAX is an empty tree.  nodes[p] describes table row p (parent
+// UINT32_MAX: reached from no root); problems lists the reached pages with any
+// bit set, ascending by page id, at most max_listed of them; n_problems is
+// always full.  The bits are enum pcs_tree_bits of eloqstore_pcs.h.
+struct TreeNode {
+    uint32_t parent = UINT32_MAX;
+    uint8_t depth = 0xFF, tree = 0xFF, type = 0xFF, bits = 0;
+    uint32_t n_children = 0, n_bad_children = 0;
+};
+struct TreeProblem {
+    uint32_t page_id = 0, parent = 0, bits = 0, depth = 0;
+};
+struct TreeReport {
+    uint64_t n_pages = 0, table_size = 0, n_mapped = 0, n_reached = 0;
+    uint64_t n_nonleaf = 0, n_leaf_index = 0, n_data = 0;
+    uint64_t n_refs = 0, n_extra_refs = 0, n_out_of_range_refs = 0;
+    uint64_t max_depth = UINT64_MAX, n_depth_capped = 0;
+    uint64_t n_by_bit[8] = {};
+    uint64_t n_problems = 0, first_problem = UINT64_MAX;
+    uint64_t n_unreached_mapped = 0, unreached_by_type[6] = {}, n_unreached_unread = 0;
+    uint64_t n_chain_heads = 0;
+    std::vector<TreeProblem> problems;
+    std::vector<TreeNode> nodes;
+};
+int TryCheckTree(std::span<const uint8_t> pages, size_t page_size, uint64_t fp_first,
+                 std::span<const uint8_t> classes, std::span<const uint64_t> table, std::span<const uint64_t> roots,
+                 TreeReport& report, size_t max_listed = 1024);
+TreeReport CheckTree(std::span<const uint8_t> pages, size_t page_size, uint64_t fp_first,
+                     std::span<const uint8_t> classes, std::span<const uint64_t> table,
+                     std::span<const uint64_t> roots, size_t max_listed = 1024);
+
 // Registers a page-pool chunk or io_uring buffer ring once (PagesPool::Extend,
 // src/storage/page.cpp:95-120): batches whose pages all lie in registered
 // memory are then hashed in place over PCIe in one launch, with no gather

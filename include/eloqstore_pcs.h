@@ -108,7 +108,10 @@ enum pcs_flags {
  *      dlsym: pcs_manifest_replay_dev / pcs_manifest_replay_host, enum
  *      pcs_replay_status, struct pcs_replay_report and pcs_replay_summary;
  *      pcs_scrub_live_dev / pcs_scrub_live_host, struct pcs_live_page and
- *      pcs_live_summary; PCS_TUNE_REPLAY_TILE */
+ *      pcs_live_summary; PCS_TUNE_REPLAY_TILE; pcs_tree_check_dev /
+ *      pcs_tree_check_host, enum pcs_tree_bits, struct pcs_tree_node,
+ *      pcs_tree_problem and pcs_tree_summary, PCS_TREE_MAX_DEPTH and
+ *      PCS_TREE_CLASS_ABSENT */
 #define PCS_ABI_VERSION 7
 int pcs_abi_version(void);
 const char *pcs_version(void);
@@ -717,6 +720,135 @@ int pcs_scrub_live_dev(const uint8_t *d_class, uint64_t n_pages, uint64_t fp_fir
 int pcs_scrub_live_host(const uint8_t *cls, uint64_t n_pages, uint64_t fp_first, const uint64_t *table,
                         uint64_t table_size, uint32_t *owner /* may be NULL */, pcs_live_summary *summary,
                         pcs_live_page *damaged, uint64_t damaged_cap);
+
+/* ---- tree check: walk the index tree from the replayed roots ------------------
+ * After a replay the device holds the mapping table, root and ttl_root; after a
+ * scrub a class byte per file page.  The tree check looks inside the pages: it
+ * walks the B-tree that hangs off every root breadth-first, level by level, and
+ * reports what does not hold together.  d_pages / d_class describe the file
+ * pages fp_first .. fp_first + n_pages (scrub live's window convention),
+ * d_table is a replayed table (a row maps file page value >> 3 iff value & 7 ==
+ * 1), d_roots a DEVICE array of n_roots logical page ids: root and ttl_root are
+ * adjacent words of a pcs_replay_report, so &report->root with n_roots = 2
+ * chains a replay into the check with no host round trip.  A root >= UINT32_MAX
+ * is an empty tree; a smaller root >= table_size is counted in n_refs and
+ * n_out_of_range_refs and reaches nothing.
+ *
+ * Page rules (IndexPageBuilder, src/storage/index_page_builder.cpp:44-204;
+ * IndexPageIter, src/storage/mem_index_page.cpp:134-233; the data-page header,
+ * include/storage/data_page.h:26-51), little-endian: an index page has type
+ * byte (offset 8) 0 (NonLeafIndex) or 1 (LeafIndex), content length C = LE16
+ * @9 with 17 <= C <= page_size, R = LE16 @(C - 2) restart offsets o[k] = LE16
+ * @(E + 2k) from E = C - 2 (1 + R) >= 15, and child 0 = LE32 @11.  R == 0
+ * requires E == 15; otherwise o[0] == 15, o[k] < o[k + 1], o[R - 1] < E, and
+ * every region [o[k], o[k + 1]) (o[R] = E) is a whole number of entries varint32
+ * shared | varint32 non_shared | non_shared key bytes | varint32 v, each varint
+ * at most 5 bytes and inside the region, shared == 0 in a region's first entry
+ * and <= the previous entry's key length otherwise; delta = (v & 1) ? -(v >> 1)
+ * : (v >> 1); the child id is delta in a region's first entry, previous id +
+ * delta otherwise, and lies in [0, INT32_MAX].  On such a page the regions
+ * decode independently and yield exactly the children the reference's
+ * sequential iterator yields.  A page that breaks any rule is MALFORMED and
+ * contributes NO child; no byte outside the page is read.  Key order is not
+ * checked.  Of a data page (type 2) only prev = LE32 @11 and next = LE32 @15
+ * are read.
+ *
+ * The walk: a logical page c < table_size referenced at depth d by parent p
+ * bids the key (d << 32 | p); the smallest key claims it (a root bids depth 0
+ * with its own id as parent; of equal roots the lowest tree index wins), so the
+ * winner is the smallest depth, then the lowest parent id, whatever the
+ * schedule; `tree` is the winner's tree.  Every page is decoded once: cycles
+ * are harmless.  At most PCS_TREE_MAX_DEPTH levels are decoded: an index page
+ * claimed at depth 16 is typed, counted in n_depth_capped and not decoded.  For
+ * a claimed page the first rule that applies sets one bit, and the page is then
+ * neither read nor followed:
+ *   UNMAPPED    its table value is not a file page
+ *   ABSENT      the file page lies outside the window, or its class byte is
+ *               none of 0, 1, 2 (PCS_TREE_CLASS_ABSENT is the byte to write for
+ *               pages that were not loaded)
+ *   BLANK       class byte 2
+ *   CORRUPT     class byte 0
+ *   WRONG_TYPE  class byte 1 and the type byte does not fit: a root and a child
+ *               of a type-0 page are of type 0 or 1, a child of a type-1 page
+ *               is of type 2
+ *   MALFORMED   an index page of the right type that breaks the page rule
+ * A well-formed index page at depth < 16 has its children bid; a child id >=
+ * table_size sets BAD_CHILD on the PARENT.  After the walk a reached data page
+ * d with none of the six bits above gets BAD_LINK unless next == UINT32_MAX or
+ * next is a reached data page with none of those bits whose prev == d, and the
+ * same for prev with the roles swapped.  Chain heads (prev == UINT32_MAX) are
+ * counted; tails equal heads in any consistent chain set and are not reported.
+ *
+ * d_nodes[p] (one per table row, may be NULL) describes row p; a row reached
+ * from no root has parent UINT32_MAX, depth, tree and type 0xFF and zeros
+ * elsewhere.  d_problems[0 .. n_listed) are the reached nodes with bits != 0 in
+ * ascending page_id, capped at problem_cap (may be NULL iff problem_cap == 0);
+ * entries at n_listed and beyond are not written.  Every output is the same
+ * from call to call (claims by atomicMin, the list by ordered compaction).
+ * unreached_by_type counts the mapped rows no root reaches whose page is in the
+ * window with class byte 1, by the scrub's six type buckets; overflow pages hang
+ * off data-page entries, which are not decoded, so bucket 3 is expected to be
+ * non-zero, while an unreached mapped index or data page is a leak or a lost
+ * subtree.
+ *
+ * Limits (PCS_ERR_INVALID): 32 <= page_size <= 65535, table_size <= 2^32 - 1,
+ * 1 <= n_roots <= 8; n_pages == 0 and table_size == 0 are legal.  d_table,
+ * d_roots, d_nodes, d_summary and d_problems are 8-byte aligned; d_pages and
+ * d_class may have any alignment.  The _dev form never synchronises: a fixed
+ * number of launches of fixed size, no count read back; its scratch is
+ * event-fenced per stream (at most 28 bytes per table row).  One wavefront decodes one
+ * page, so one huge page keeps one CU busy.
+ *
+ * pcs_tree_check_host takes host pointers; `pages` is ONE contiguous buffer of
+ * n_pages * page_size bytes, copied to the device with one plain copy (the
+ * whole window must be resident: PCS_ERR_NOMEM when it does not fit; the staged
+ * pipeline of the other host batches is not used).  With cls == NULL the pages
+ * are scrubbed on the device first (page_size >= 249 then).  roots is a host
+ * array.  PCS_TUNE_FAIL_INJECT applies to it. */
+#define PCS_TREE_MAX_DEPTH 16
+#define PCS_TREE_CLASS_ABSENT 3
+enum pcs_tree_bits {
+    PCS_TREE_UNMAPPED = 1, PCS_TREE_ABSENT = 2, PCS_TREE_BLANK = 4, PCS_TREE_CORRUPT = 8,
+    PCS_TREE_WRONG_TYPE = 16, PCS_TREE_MALFORMED = 32, PCS_TREE_BAD_CHILD = 64, PCS_TREE_BAD_LINK = 128,
+};
+typedef struct pcs_tree_node { /* 16 bytes, one per table row */
+    uint32_t parent;           /* UINT32_MAX: reached from no root; a root is its own parent */
+    uint8_t depth, tree;       /* 0xFF when not reached */
+    uint8_t type;              /* page byte 8; 0xFF when the page was not read */
+    uint8_t bits;              /* pcs_tree_bits */
+    uint32_t n_children;       /* child pointers decoded, leftmost included; 0 unless a well-formed index page */
+    uint32_t n_bad_children;   /* of them >= table_size */
+} pcs_tree_node;
+typedef struct pcs_tree_problem { /* reached nodes with bits != 0, ascending page_id, capped */
+    uint32_t page_id, parent, bits, depth;
+} pcs_tree_problem;
+typedef struct pcs_tree_summary { /* 32 x u64, the same layout on device and host; n_roots, the caller's own
+                                    argument, has no word here */
+    uint64_t n_pages, table_size, n_mapped, n_reached;
+    uint64_t n_nonleaf, n_leaf_index, n_data; /* reached, bits == 0, by type */
+    uint64_t n_refs;                /* child pointers decoded plus the non-empty roots */
+    uint64_t n_extra_refs;          /* in-range refs beyond the first to a page */
+    uint64_t n_out_of_range_refs;   /* refs >= table_size */
+    uint64_t max_depth;             /* UINT64_MAX when nothing was reached */
+    uint64_t n_depth_capped;
+    uint64_t n_by_bit[8];           /* reached nodes with bit 1 << k set */
+    uint64_t n_problems;
+    uint64_t first_problem;         /* smallest page_id with bits != 0, UINT64_MAX when none */
+    uint64_t n_listed;              /* min(n_problems, problem_cap) */
+    uint64_t n_unreached_mapped;    /* mapped rows reached from no root = the sum of the next seven words */
+    uint64_t unreached_by_type[6];  /* in the window, class byte 1: the scrub's six type buckets */
+    uint64_t n_unreached_unread;    /* outside the window or class byte != 1 */
+    uint64_t n_chain_heads;
+} pcs_tree_summary;
+int pcs_tree_check_dev(const void *d_pages, uint64_t page_size, uint64_t n_pages, uint64_t fp_first,
+                       const uint8_t *d_class, const uint64_t *d_table, uint64_t table_size,
+                       const uint64_t *d_roots, uint32_t n_roots, pcs_tree_node *d_nodes /* may be NULL */,
+                       pcs_tree_summary *d_summary, pcs_tree_problem *d_problems, uint64_t problem_cap,
+                       pcs_stream_t stream);
+int pcs_tree_check_host(const void *pages, uint64_t page_size, uint64_t n_pages, uint64_t fp_first,
+                        const uint8_t *cls /* may be NULL */, const uint64_t *table, uint64_t table_size,
+                        const uint64_t *roots, uint32_t n_roots, pcs_tree_node *nodes /* may be NULL */,
+                        pcs_tree_summary *summary, pcs_tree_problem *problems, uint64_t problem_cap);
 
 /* ---- sharding ------------------------------------------------------------
  * Contiguous page range [begin, end) of rank `rank` of `world` for n pages:

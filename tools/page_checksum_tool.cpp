@@ -60,6 +60,22 @@
 //       max_fp_id, the mapped pages and how many of them lie in files not
 //       given.  Exit 2 if any live page is corrupt, else 3 if any is blank,
 //       else 0; dead damage never fails the run.
+//   page_checksum_tool --tree <manifest> <page_size> <pages_per_file_shift> <data_file>...
+//       does the index tree that hangs off the replayed roots hold together?
+//       The manifest is replayed as for --live (the same refusal line, exit 2).
+//       The given files are loaded into ONE window that spans their file ids,
+//       [min_id << shift, (max_id + 1) << shift); pages of files not given (and
+//       pages past the end of a short file) get class byte 3 and are reported
+//       ABSENT when the tree points to them.  A span that does not fit in
+//       device memory: a message, exit 1.  The files are scrubbed, the tree
+//       check runs on root and ttl_root (pcs_tree_check_host), and the tool
+//       prints one line per tree, one line per problem (page id, parent, depth,
+//       bit names) and a last line with the unreached mapped pages by type.
+//       Exit 2 when a reached page is corrupt, malformed, of the wrong type,
+//       unmapped or has a child beyond the table; else 3 when a reached page is
+//       blank; else 0.  ABSENT (nothing was checked) and BAD_LINK (no store
+//       written by the reference was at hand to confirm that every committed
+//       state keeps the sibling links) are printed and never change the status.
 //   --scan/--stamp print a summary line with the GiB/s of the call; exit codes
 //   as above (--scan: 2 if any page is corrupted).
 #include <fcntl.h>
@@ -84,6 +100,7 @@
 #include "manifest_replay.h"
 #include "manifest_scan.h"
 #include "scrub_merge.h"
+#include "tree_check.h"
 
 namespace {
 
@@ -116,8 +133,13 @@ void usage(const char* prog) {
                  "           several: a line per file (exit 2: broken or bad snapshot, 3: torn tail, 1: empty)\n"
                  "       %s --live <manifest_file> <page_size_bytes> <pages_per_file_shift> <data_file>...\n"
                  "           exit 2: a mapped page is corrupt or the manifest cannot be replayed; exit 3: a mapped\n"
-                 "           page is blank; damage in pages the manifest no longer maps never fails the run\n",
-                 prog, prog, prog, prog, prog, prog, prog, prog);
+                 "           page is blank; damage in pages the manifest no longer maps never fails the run\n"
+                 "       %s --tree <manifest_file> <page_size_bytes> <pages_per_file_shift> <data_file>...\n"
+                 "           walks the index tree from root and ttl_root; exit 2: a reached page is corrupt,\n"
+                 "           malformed, of the wrong type, unmapped or points beyond the table; exit 3: a reached\n"
+                 "           page is blank.  absent pages (files not given) and bad-link (sibling links: not\n"
+                 "           confirmed against a store written by the reference) are printed, never fail the run\n",
+                 prog, prog, prog, prog, prog, prog, prog, prog, prog);
 }
 
 constexpr uint64_t kDefaultPageSize = 4096;  // KvOptions{}.data_page_size
@@ -720,41 +742,21 @@ static bool read_whole(const char* path, std::vector<char>& bytes) {
     return true;
 }
 
-// --live: replay the manifest, scrub every data file, and ask of each file's
-// class bytes which pages the replayed table still points to.
-int live(const char* manifest, const char* size_s, const char* shift_s, int n_files, char** files) {
+// The table, root and ttl_root a manifest describes: 0, or the exit code after
+// the message (1) or the one line that says why it cannot be replayed (2).
+int replay_manifest(const char* manifest, pcs_replay_report& rep, std::vector<uint64_t>& table) {
     constexpr uint32_t kPageAlign = 4096;
-    uint64_t page_size = 0, shift = 0;
-    if (!parse_u64(size_s, page_size) || page_size == 0 || !parse_u64(shift_s, shift) || shift > 40) {
-        std::fprintf(stderr, "Invalid page size or pages_per_file_shift\n");
-        return 1;
-    }
-    std::vector<uint64_t> ids(n_files);
-    for (int f = 0; f < n_files; ++f) {
-        uint64_t term = 0;
-        if (!pcs::live_parse_data_file(files[f], ids[f], term)) {
-            std::fprintf(stderr, "Not a data file name (data_<file_id>_<term>): %s\n", files[f]);
-            return 1;
-        }
-        for (int g = 0; g < f; ++g) {
-            if (ids[g] == ids[f]) {  // its mapped pages would be counted twice
-                std::fprintf(stderr, "File id %llu is given twice: %s\n", (unsigned long long)ids[f], files[f]);
-                return 1;
-            }
-        }
-    }
     std::vector<char> image;
     if (!read_whole(manifest, image)) return 1;
     const void* ptr = image.data();
     const uint64_t size = image.size();
-    pcs_replay_report rep{};
     pcs_replay_summary sum{};
     // the rows are not known before the replay: ask without a table first
     if (const int rc = pcs_manifest_replay_host(&ptr, &size, 1, kPageAlign, nullptr, &rep, &sum, nullptr, 0)) {
         std::fprintf(stderr, "Manifest replay failed (%d): %s\n", rc, pcs_last_error());
         return 1;
     }
-    std::vector<uint64_t> table(rep.status == PCS_REPLAY_TABLE_CAP ? rep.table_size : 0);
+    table.assign(rep.status == PCS_REPLAY_TABLE_CAP ? rep.table_size : 0, 0);
     if (!table.empty()) {
         if (const int rc = pcs_manifest_replay_host(&ptr, &size, 1, kPageAlign, nullptr, &rep, &sum, table.data(),
                                                     table.size())) {
@@ -767,6 +769,41 @@ int live(const char* manifest, const char* size_s, const char* shift_s, int n_fi
         std::fputs(refusal.c_str(), stdout);
         return 2;
     }
+    return 0;
+}
+
+// parses the data file names of --live and --tree: false after the message
+bool data_file_ids(int n_files, char** files, std::vector<uint64_t>& ids) {
+    ids.assign(n_files, 0);
+    for (int f = 0; f < n_files; ++f) {
+        uint64_t term = 0;
+        if (!pcs::live_parse_data_file(files[f], ids[f], term)) {
+            std::fprintf(stderr, "Not a data file name (data_<file_id>_<term>): %s\n", files[f]);
+            return false;
+        }
+        for (int g = 0; g < f; ++g) {
+            if (ids[g] == ids[f]) {  // its mapped pages would be counted twice
+                std::fprintf(stderr, "File id %llu is given twice: %s\n", (unsigned long long)ids[f], files[f]);
+                return false;
+            }
+        }
+    }
+    return true;
+}
+
+// --live: replay the manifest, scrub every data file, and ask of each file's
+// class bytes which pages the replayed table still points to.
+int live(const char* manifest, const char* size_s, const char* shift_s, int n_files, char** files) {
+    uint64_t page_size = 0, shift = 0;
+    if (!parse_u64(size_s, page_size) || page_size == 0 || !parse_u64(shift_s, shift) || shift > 40) {
+        std::fprintf(stderr, "Invalid page size or pages_per_file_shift\n");
+        return 1;
+    }
+    std::vector<uint64_t> ids;
+    if (!data_file_ids(n_files, files, ids)) return 1;
+    pcs_replay_report rep{};
+    std::vector<uint64_t> table;
+    if (const int rc = replay_manifest(manifest, rep, table)) return rc;
     std::vector<pcs_live_summary> sums;
     uint64_t mapped_in_files = 0;
     for (int f = 0; f < n_files; ++f) {
@@ -802,7 +839,110 @@ int live(const char* manifest, const char* size_s, const char* shift_s, int n_fi
     return pcs::live_tool_exit(sums.data(), sums.size());
 }
 
+// --tree: replay the manifest, load the given data files into one window,
+// scrub them and walk the index tree from root and ttl_root.
+int tree(const char* manifest, const char* size_s, const char* shift_s, int n_files, char** files) {
+    uint64_t page_size = 0, shift = 0;
+    if (!parse_u64(size_s, page_size) || page_size == 0 || !parse_u64(shift_s, shift) || shift > 40) {
+        std::fprintf(stderr, "Invalid page size or pages_per_file_shift\n");
+        return 1;
+    }
+    std::vector<uint64_t> ids;
+    if (!data_file_ids(n_files, files, ids)) return 1;
+    pcs_replay_report rep{};
+    std::vector<uint64_t> table;
+    if (const int rc = replay_manifest(manifest, rep, table)) return rc;
+    const uint64_t lo = *std::min_element(ids.begin(), ids.end()), hi = *std::max_element(ids.begin(), ids.end());
+    const uint64_t per_file = 1ull << shift, fp_first = lo << shift;
+    const char* too_large = "The span of the given files does not fit in device memory\n";
+    if ((hi - lo + 1) > (1ull << 40) / per_file / page_size) {
+        std::fputs(too_large, stderr);
+        return 1;
+    }
+    const uint64_t n_pages = (hi - lo + 1) * per_file;
+    std::vector<char> window;
+    std::vector<uint8_t> cls;
+    try {
+        window.assign(n_pages * page_size, 0);
+        cls.assign(n_pages, PCS_TREE_CLASS_ABSENT);
+    } catch (const std::bad_alloc&) {
+        std::fputs(too_large, stderr);
+        return 1;
+    }
+    for (int f = 0; f < n_files; ++f) {
+        std::vector<char> bytes;
+        if (!read_whole(files[f], bytes)) return 1;
+        const uint64_t n = bytes.size() / page_size;
+        if (n > per_file) {
+            std::fprintf(stderr, "%s holds more than 1 << %llu pages\n", files[f], (unsigned long long)shift);
+            return 1;
+        }
+        const uint64_t first = (ids[f] - lo) * per_file;
+        std::memcpy(window.data() + first * page_size, bytes.data(), n * page_size);
+        std::vector<const void*> pages(n);
+        for (uint64_t p = 0; p < n; ++p) pages[p] = window.data() + (first + p) * page_size;
+        pcs_scrub_summary ssum{};
+        if (const int rc = pcs_pages_scrub_host(pages.data(), page_size, n, cls.data() + first, nullptr, &ssum, nullptr, 0)) {
+            std::fprintf(stderr, "Scrub of %s failed (%d): %s\n", files[f], rc, pcs_last_error());
+            return 1;
+        }
+    }
+    const uint64_t roots[2] = {rep.root, rep.ttl_root};
+    std::vector<pcs_tree_node> nodes(table.size());
+    std::vector<pcs_tree_problem> problems(table.size());
+    pcs_tree_summary sum{};
+    const int rc = pcs_tree_check_host(window.data(), page_size, n_pages, fp_first, cls.data(), table.data(), table.size(),
+                                       roots, 2, nodes.data(), &sum, problems.data(), problems.size());
+    if (rc == PCS_ERR_NOMEM) {
+        std::fputs(too_large, stderr);
+        return 1;
+    }
+    if (rc) {
+        std::fprintf(stderr, "Tree check failed (%d): %s\n", rc, pcs_last_error());
+        return 1;
+    }
+    static const char* const tree_name[2] = {"root", "ttl_root"};
+    for (int t = 0; t < 2; ++t) {
+        if (roots[t] >= UINT32_MAX) {
+            std::printf("tree %s none\n", tree_name[t]);
+            continue;
+        }
+        uint64_t reached = 0, by_type[3] = {}, bad = 0, depth = 0;
+        for (const pcs_tree_node& n : nodes) {
+            if (n.parent == UINT32_MAX || n.tree != t) continue;
+            ++reached;
+            depth = std::max<uint64_t>(depth, n.depth);
+            if (n.bits) ++bad;
+            else if (n.type < 3) ++by_type[n.type];
+        }
+        std::printf("tree %s %llu reached %llu nonleaf %llu leaf_index %llu data %llu problems %llu max_depth %llu\n",
+                    tree_name[t], (unsigned long long)roots[t], (unsigned long long)reached,
+                    (unsigned long long)by_type[0], (unsigned long long)by_type[1], (unsigned long long)by_type[2],
+                    (unsigned long long)bad, (unsigned long long)depth);
+    }
+    for (uint64_t k = 0; k < sum.n_listed; ++k) {
+        char names[96];
+        pcs::tree_bit_names(problems[k].bits, names);
+        std::printf("  problem: page_id %u parent %u depth %u %s\n", problems[k].page_id, problems[k].parent,
+                    problems[k].depth, names);
+    }
+    std::printf("unreached mapped %llu nonleaf %llu leaf_index %llu data %llu overflow %llu deleted %llu other %llu "
+                "unread %llu\n",
+                (unsigned long long)sum.n_unreached_mapped, (unsigned long long)sum.unreached_by_type[0],
+                (unsigned long long)sum.unreached_by_type[1], (unsigned long long)sum.unreached_by_type[2],
+                (unsigned long long)sum.unreached_by_type[3], (unsigned long long)sum.unreached_by_type[4],
+                (unsigned long long)sum.unreached_by_type[5], (unsigned long long)sum.n_unreached_unread);
+    return pcs::tree_tool_exit(sum);
+}
+
 int main(int argc, char** argv) {
+    if (argc >= 2 && !std::strcmp(argv[1], "--tree")) {
+        if (argc < 6) {
+            usage(argv[0]);
+            return 1;
+        }
+        return tree(argv[2], argv[3], argv[4], argc - 5, argv + 5);
+    }
     if (argc >= 2 && !std::strcmp(argv[1], "--live")) {
         if (argc < 6) {
             usage(argv[0]);
