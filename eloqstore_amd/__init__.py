@@ -89,6 +89,8 @@ _SIGS = {
     "pcs_scrub_live_host": [_vp, _u64, _u64, _vp, _u64, _vp, _vp, _vp, _u64],
     "pcs_tree_check_dev": [_vp, _u64, _u64, _u64, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _u64, _vp],
     "pcs_tree_check_host": [_vp, _u64, _u64, _u64, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _u64],
+    "pcs_leaf_check_dev": [_vp, _u64, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp],
+    "pcs_leaf_check_host": [_vp, _u64, _u64, _u64, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u64],
     "pcs_set_tuning": [_i32, ctypes.c_int64],
     "pcs_get_tuning": [_i32],
     "pcs_counter": [_i32],
@@ -809,6 +811,98 @@ def tree_check_host(pages, page_size: int, fp_first: int, cls, table, roots, pro
           roots.ctypes.data, roots.size, nodes.ctypes.data if want_nodes else 0, summary.ctypes.data,
           problems.ctypes.data if problem_cap else 0, problem_cap)
     return (nodes[: table.size] if want_nodes else None), summary[0], problems[: int(summary[0]["n_listed"])]
+
+
+# pcs_leaf_node (16 bytes), pcs_leaf_problem (16 bytes), pcs_leaf_summary (32 u64 words)
+LEAF_NODE_DTYPE = np.dtype([("owner", "<u4"), ("owner_entry", "<u2"), ("bits", "<u2"), ("a", "<u4"), ("b", "<u4")])
+LEAF_PROBLEM_DTYPE = np.dtype([("page_id", "<u4"), ("owner", "<u4"), ("bits", "<u4"), ("owner_entry", "<u4")])
+LEAF_SUMMARY_DTYPE = np.dtype([
+    ("n_pages", "<u8"), ("table_size", "<u8"), ("n_data_pages", "<u8"), ("n_data_ok", "<u8"), ("n_entries", "<u8"),
+    ("n_overflow_values", "<u8"), ("n_expiring", "<u8"), ("n_compressed", "<u8"), ("inline_value_bytes", "<u8"),
+    ("overflow_value_bytes", "<u8"), ("n_refs", "<u8"), ("n_out_of_range_refs", "<u8"), ("n_extra_refs", "<u8"),
+    ("n_refs_to_tree", "<u8"), ("n_misplaced_pointers", "<u8"), ("n_chain_capped", "<u8"), ("max_groups", "<u8"),
+    ("n_overflow_pages", "<u8"), ("n_by_bit", "<u8", (9,)), ("n_problems", "<u8"), ("first_problem", "<u8"),
+    ("n_listed", "<u8"), ("n_leaked_overflow", "<u8"), ("n_overflow_ok", "<u8")])
+LEAF_BAD_POINTER, LEAF_BAD_CHAIN, LEAF_SHARED = 64, 128, 256   # the low six bits are TREE_UNMAPPED .. TREE_MALFORMED
+LEAF_MAX_GROUPS = 4096
+
+
+def leaf_check_async(pages, page_size: int, n_pages: int, fp_first: int, cls, table, tree_nodes,
+                     table_size: int | None = None, leaves=None, summary=None, problems=None,
+                     problem_cap: int = 1024, stream=None):
+    """pcs_leaf_check_dev, enqueue only: pages, cls and table as for
+    tree_check_async, tree_nodes the node tensor a tree check over the same
+    inputs wrote (on the same stream, or one this stream waits for); returns the
+    device tensors (leaves table_size x 2 int64 words, or None when leaves is
+    False; the 32 summary words; the problems as problem_cap x 2 int64 words),
+    valid once the stream is synchronised."""
+    device = summary.device if summary is not None else cls.device if cls is not None else table.device
+    if table_size is None:
+        table_size = 0 if table is None else table.numel()
+    if leaves is None:
+        leaves = torch.empty((max(table_size, 1), 2), dtype=torch.int64, device=device)
+    if summary is None:
+        summary = torch.empty(32, dtype=torch.int64, device=device)
+    if problems is None and problem_cap:
+        problems = torch.empty((problem_cap, 2), dtype=torch.int64, device=device)
+    _call("pcs_leaf_check_dev", _ptr(pages) if n_pages else 0, page_size, n_pages, fp_first,
+          _ptr(cls) if n_pages else 0, _ptr(table) if table_size else 0, table_size,
+          _ptr(tree_nodes) if table_size else 0, _ptr(None if leaves is False else leaves), _ptr(summary),
+          _ptr(problems) if problem_cap else 0, problem_cap, _stream(stream))
+    return (None if leaves is False else leaves), summary, problems
+
+
+def leaf_check(pages, page_size: int, n_pages: int, fp_first: int, cls, table, tree_nodes, leaves=None,
+               problem_cap: int = 1024, stream=None):
+    """Decode the data pages a tree check reached and walk their overflow chains
+    over device pages -> (leaves (LEAF_NODE_DTYPE, one per table row; None when
+    leaves is False), summary (one LEAF_SUMMARY_DTYPE record), the n_listed
+    problems (LEAF_PROBLEM_DTYPE)).  table may be a device tensor or a host
+    array; tree_nodes is tree_check_async's device tensor.  Waits for the
+    stream."""
+    device = pages.device
+    if table is not None and not isinstance(table, torch.Tensor):
+        table = torch.from_numpy(np.ascontiguousarray(table, dtype=np.uint64).view(np.int64).copy()).to(device)
+    table_size = 0 if table is None else table.numel()
+    leaves, summary, problems = leaf_check_async(pages, page_size, n_pages, fp_first, cls, table, tree_nodes,
+                                                 table_size, leaves, None, None, problem_cap, stream)
+    if stream is not None:
+        _call("pcs_synchronize", _stream(stream))
+    s = np.ascontiguousarray(summary.cpu().numpy()).view(np.uint64).view(LEAF_SUMMARY_DTYPE)[0]
+    listed = int(s["n_listed"])
+    probs = (np.ascontiguousarray(problems[:listed].cpu().numpy()).view(np.uint8).view(LEAF_PROBLEM_DTYPE).reshape(-1)
+             if listed else np.zeros(0, dtype=LEAF_PROBLEM_DTYPE))
+    lv = None
+    if leaves is not None:
+        lv = (np.ascontiguousarray(leaves[:table_size].cpu().numpy()).view(np.uint8).view(LEAF_NODE_DTYPE).reshape(-1)
+              if table_size else np.zeros(0, dtype=LEAF_NODE_DTYPE))
+    return lv, s, probs
+
+
+def leaf_check_host(pages, page_size: int, fp_first: int, cls, table, roots, problem_cap: int = 1024,
+                    want_nodes: bool = True):
+    """pcs_leaf_check_host over host arrays (pages one contiguous uint8 buffer;
+    cls None scrubs the pages on the device): the tree check and the leaf check
+    in one call -> (tree nodes, tree summary, leaves, leaf summary, leaf
+    problems); both node arrays are None when want_nodes is False."""
+    pages = np.ascontiguousarray(pages, dtype=np.uint8).reshape(-1)
+    n = pages.size // page_size
+    if cls is not None:
+        cls = np.ascontiguousarray(cls, dtype=np.uint8)
+    table = np.ascontiguousarray(table, dtype=np.uint64)
+    roots = np.ascontiguousarray(roots, dtype=np.uint64)
+    tree_nodes = np.zeros(max(1, table.size), dtype=TREE_NODE_DTYPE)
+    tree_summary = np.zeros(1, dtype=TREE_SUMMARY_DTYPE)
+    leaves = np.zeros(max(1, table.size), dtype=LEAF_NODE_DTYPE)
+    summary = np.zeros(1, dtype=LEAF_SUMMARY_DTYPE)
+    problems = np.zeros(max(1, problem_cap), dtype=LEAF_PROBLEM_DTYPE)
+    _call("pcs_leaf_check_host", pages.ctypes.data if n else 0, page_size, n, fp_first,
+          cls.ctypes.data if cls is not None and n else 0, table.ctypes.data if table.size else 0, table.size,
+          roots.ctypes.data, roots.size, tree_nodes.ctypes.data if want_nodes else 0, tree_summary.ctypes.data,
+          leaves.ctypes.data if want_nodes else 0, summary.ctypes.data, problems.ctypes.data if problem_cap else 0,
+          problem_cap)
+    return ((tree_nodes[: table.size] if want_nodes else None), tree_summary[0],
+            (leaves[: table.size] if want_nodes else None), summary[0], problems[: int(summary[0]["n_listed"])])
 
 
 class Batch:

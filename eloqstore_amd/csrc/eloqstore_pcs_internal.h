@@ -108,6 +108,15 @@ hipError_t run_scrub_live(const uint8_t* cls, uint64_t n, uint64_t fp_first, con
 hipError_t run_tree_check(const uint8_t* pages, uint64_t page_size, uint64_t n, uint64_t fp_first, const uint8_t* cls,
                           const uint64_t* table, uint64_t rows, const uint64_t* roots, uint32_t n_roots,
                           uint64_t* nodes, uint64_t* summary, uint64_t* list, uint64_t cap, hipStream_t s);
+// Leaf check (leaf_check.hip) over the same window, class bytes and table, with
+// tree_nodes = the 2 words per row a tree check wrote (required when rows > 0;
+// only read): leaves = 2 words per row (pcs_leaf_node; may be null: scratch is
+// leased), summary = the 32 words of pcs_leaf_summary, list[0 ..
+// min(n_problems, cap)) = pcs_leaf_problem, ascending.  All device memory;
+// enqueues on s and never waits.
+hipError_t run_leaf_check(const uint8_t* pages, uint64_t page_size, uint64_t n, uint64_t fp_first, const uint8_t* cls,
+                          const uint64_t* table, uint64_t rows, const uint64_t* tree_nodes, uint64_t* leaves,
+                          uint64_t* summary, uint64_t* list, uint64_t cap, hipStream_t s);
 // Event-fenced device scratch (see ScratchPool in pcs_kernels.hip): the
 // buffer is reused only after the work queued on `s` at release completes.
 hipError_t scratch_acquire(size_t bytes, void** out, int* id);

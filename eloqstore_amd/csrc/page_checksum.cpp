@@ -345,6 +345,8 @@ LiveReport ScrubLive(std::span<const uint8_t> classes, uint64_t fp_first, std::s
     return report;
 }
 
+static void fill_tree_report(const pcs_tree_summary& sum, TreeReport& report);
+
 int TryCheckTree(std::span<const uint8_t> pages, size_t page_size, uint64_t fp_first,
                  std::span<const uint8_t> classes, std::span<const uint64_t> table, std::span<const uint64_t> roots,
                  TreeReport& report, size_t max_listed) {
@@ -362,6 +364,13 @@ int TryCheckTree(std::span<const uint8_t> pages, size_t page_size, uint64_t fp_f
                                        reinterpret_cast<pcs_tree_node*>(report.nodes.data()), &sum,
                                        reinterpret_cast<pcs_tree_problem*>(report.problems.data()), max_listed);
     if (rc != PCS_OK) return rc;
+    fill_tree_report(sum, report);
+    report.problems.resize(sum.n_listed);
+    return PCS_OK;
+}
+
+// the counters of a pcs_tree_summary into a TreeReport (problems and nodes are the caller's)
+static void fill_tree_report(const pcs_tree_summary& sum, TreeReport& report) {
     report.n_pages = sum.n_pages;
     report.table_size = sum.table_size;
     report.n_mapped = sum.n_mapped;
@@ -381,8 +390,6 @@ int TryCheckTree(std::span<const uint8_t> pages, size_t page_size, uint64_t fp_f
     for (int k = 0; k < 6; ++k) report.unreached_by_type[k] = sum.unreached_by_type[k];
     report.n_unreached_unread = sum.n_unreached_unread;
     report.n_chain_heads = sum.n_chain_heads;
-    report.problems.resize(sum.n_listed);
-    return PCS_OK;
 }
 
 TreeReport CheckTree(std::span<const uint8_t> pages, size_t page_size, uint64_t fp_first,
@@ -391,6 +398,70 @@ TreeReport CheckTree(std::span<const uint8_t> pages, size_t page_size, uint64_t 
     TreeReport report;
     if (int rc = TryCheckTree(pages, page_size, fp_first, classes, table, roots, report, max_listed))
         die("CheckTree", rc);
+    return report;
+}
+
+int TryCheckLeaves(std::span<const uint8_t> pages, size_t page_size, uint64_t fp_first,
+                   std::span<const uint8_t> classes, std::span<const uint64_t> table, std::span<const uint64_t> roots,
+                   LeafReport& report, size_t max_listed) {
+    static_assert(sizeof(LeafNode) == sizeof(pcs_leaf_node), "LeafNode mirrors pcs_leaf_node");
+    static_assert(sizeof(LeafProblem) == sizeof(pcs_leaf_problem), "LeafProblem mirrors pcs_leaf_problem");
+    if (page_size == 0 || pages.size() % page_size) return PCS_ERR_INVALID;
+    const uint64_t n_pages = pages.size() / page_size;
+    if (!classes.empty() && classes.size() != n_pages) return PCS_ERR_INVALID;
+    report.tree.nodes.assign(table.size(), TreeNode{});
+    report.tree.problems.clear();
+    report.leaves.assign(table.size(), LeafNode{});
+    report.problems.assign(max_listed, LeafProblem{});
+    pcs_tree_summary tsum{};
+    pcs_leaf_summary sum{};
+    const int rc = pcs_leaf_check_host(pages.data(), page_size, n_pages, fp_first,
+                                       classes.empty() ? nullptr : classes.data(), table.data(), table.size(),
+                                       roots.data(), static_cast<uint32_t>(std::min<size_t>(roots.size(), UINT32_MAX)),
+                                       reinterpret_cast<pcs_tree_node*>(report.tree.nodes.data()), &tsum,
+                                       reinterpret_cast<pcs_leaf_node*>(report.leaves.data()), &sum,
+                                       reinterpret_cast<pcs_leaf_problem*>(report.problems.data()), max_listed);
+    if (rc != PCS_OK) return rc;
+    fill_tree_report(tsum, report.tree);
+    // the tree's problems are its reached nodes with any bit set, ascending: all of them, from the nodes
+    for (size_t p = 0; p < report.tree.nodes.size(); ++p) {
+        const TreeNode& n = report.tree.nodes[p];
+        if (n.parent != UINT32_MAX && n.bits)
+            report.tree.problems.push_back(TreeProblem{static_cast<uint32_t>(p), n.parent, n.bits, n.depth});
+    }
+    report.n_pages = sum.n_pages;
+    report.table_size = sum.table_size;
+    report.n_data_pages = sum.n_data_pages;
+    report.n_data_ok = sum.n_data_ok;
+    report.n_entries = sum.n_entries;
+    report.n_overflow_values = sum.n_overflow_values;
+    report.n_expiring = sum.n_expiring;
+    report.n_compressed = sum.n_compressed;
+    report.inline_value_bytes = sum.inline_value_bytes;
+    report.overflow_value_bytes = sum.overflow_value_bytes;
+    report.n_refs = sum.n_refs;
+    report.n_out_of_range_refs = sum.n_out_of_range_refs;
+    report.n_extra_refs = sum.n_extra_refs;
+    report.n_refs_to_tree = sum.n_refs_to_tree;
+    report.n_misplaced_pointers = sum.n_misplaced_pointers;
+    report.n_chain_capped = sum.n_chain_capped;
+    report.max_groups = sum.max_groups;
+    report.n_overflow_pages = sum.n_overflow_pages;
+    for (int k = 0; k < 9; ++k) report.n_by_bit[k] = sum.n_by_bit[k];
+    report.n_problems = sum.n_problems;
+    report.first_problem = sum.first_problem;
+    report.n_leaked_overflow = sum.n_leaked_overflow;
+    report.n_overflow_ok = sum.n_overflow_ok;
+    report.problems.resize(sum.n_listed);
+    return PCS_OK;
+}
+
+LeafReport CheckLeaves(std::span<const uint8_t> pages, size_t page_size, uint64_t fp_first,
+                       std::span<const uint8_t> classes, std::span<const uint64_t> table,
+                       std::span<const uint64_t> roots, size_t max_listed) {
+    LeafReport report;
+    if (int rc = TryCheckLeaves(pages, page_size, fp_first, classes, table, roots, report, max_listed))
+        die("CheckLeaves", rc);
     return report;
 }
 

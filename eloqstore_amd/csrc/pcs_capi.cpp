@@ -12,6 +12,7 @@
 #include "manifest_replay.h"
 #include "manifest_scan.h"
 #include "scrub_merge.h"
+#include "leaf_check.h"
 #include "tree_check.h"
 
 #include <hip/hip_runtime.h>
@@ -1722,6 +1723,75 @@ int host_tree_check(const void* pages, uint64_t page_size, uint64_t n_pages, uin
     return finish(e, "tree check");
 }
 
+// pcs_leaf_check_host: as host_tree_check, and the tree's nodes stay on the
+// device for the leaf check that follows on the same stream.
+int host_leaf_check(const void* pages, uint64_t page_size, uint64_t n_pages, uint64_t fp_first, const uint8_t* cls,
+                    const uint64_t* table, uint64_t table_size, const uint64_t* roots, uint32_t n_roots,
+                    pcs_tree_node* tree_nodes, pcs_tree_summary* tree_summary, pcs_leaf_node* leaves,
+                    pcs_leaf_summary* summary, pcs_leaf_problem* problems, uint64_t problem_cap) {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return hip_fail(e, "hipGetDevice");
+    Slot& slot = t_ctx[dev].slot[0];
+    if (int rc = ensure_slot(slot, 1, 1)) return rc;
+    hipStream_t s = slot.stream;
+    const uint64_t cap = std::min(problem_cap, table_size);  // no more problems than rows
+    const uint64_t page_bytes = (n_pages * page_size + 15) & ~uint64_t(15), cls_bytes = (n_pages + 7) & ~uint64_t(7);
+    void* buf = nullptr;
+    int id = -1;
+    e = pcs::scratch_acquire(page_bytes + sizeof(pcs_tree_summary) + sizeof(pcs_leaf_summary) +
+                                 sizeof(pcs_scrub_summary) + 8 * 8 + table_size * 8 +
+                                 table_size * sizeof(pcs_tree_node) + (leaves ? table_size * sizeof(pcs_leaf_node) : 0) +
+                                 cap * sizeof(pcs_leaf_problem) + cls_bytes + 16,
+                             &buf, &id);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(PCS_ERR_NOMEM, "the window does not fit in device memory");
+    }
+    uint8_t* d_pages = static_cast<uint8_t*>(buf);
+    pcs_tree_summary* d_tsum = reinterpret_cast<pcs_tree_summary*>(d_pages + page_bytes);
+    pcs_leaf_summary* d_sum = reinterpret_cast<pcs_leaf_summary*>(d_tsum + 1);
+    pcs_scrub_summary* d_ssum = reinterpret_cast<pcs_scrub_summary*>(d_sum + 1);
+    uint64_t* d_roots = reinterpret_cast<uint64_t*>(d_ssum + 1);
+    uint64_t* d_table = d_roots + 8;
+    pcs_tree_node* d_tnodes = reinterpret_cast<pcs_tree_node*>(d_table + table_size);
+    pcs_leaf_node* d_leaves = reinterpret_cast<pcs_leaf_node*>(d_tnodes + table_size);
+    pcs_leaf_problem* d_list = reinterpret_cast<pcs_leaf_problem*>(d_leaves + (leaves ? table_size : 0));
+    uint8_t* d_cls = reinterpret_cast<uint8_t*>(d_list + cap);
+    if (n_pages) e = hipMemcpyAsync(d_pages, pages, n_pages * page_size, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && n_pages && cls) e = hipMemcpyAsync(d_cls, cls, n_pages, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && n_pages && !cls)
+        e = pcs::run_scrub(d_pages, page_size, n_pages, d_cls, nullptr, reinterpret_cast<uint64_t*>(d_ssum), nullptr, 0,
+                           s);
+    if (e == hipSuccess && table_size) e = hipMemcpyAsync(d_table, table, table_size * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_roots, roots, n_roots * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)  // the tree's problems are not listed: its nodes hold them all
+        e = pcs::run_tree_check(d_pages, page_size, n_pages, fp_first, d_cls, d_table, table_size, d_roots, n_roots,
+                                reinterpret_cast<uint64_t*>(d_tnodes), reinterpret_cast<uint64_t*>(d_tsum), nullptr, 0, s);
+    if (e == hipSuccess)
+        e = pcs::run_leaf_check(d_pages, page_size, n_pages, fp_first, d_cls, d_table, table_size,
+                                reinterpret_cast<const uint64_t*>(d_tnodes),
+                                leaves ? reinterpret_cast<uint64_t*>(d_leaves) : nullptr,
+                                reinterpret_cast<uint64_t*>(d_sum), reinterpret_cast<uint64_t*>(cap ? d_list : nullptr),
+                                cap, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(summary, d_sum, sizeof(*summary), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && tree_summary)
+        e = hipMemcpyAsync(tree_summary, d_tsum, sizeof(*tree_summary), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && tree_nodes && table_size)
+        e = hipMemcpyAsync(tree_nodes, d_tnodes, table_size * sizeof(pcs_tree_node), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && leaves && table_size)
+        e = hipMemcpyAsync(leaves, d_leaves, table_size * sizeof(pcs_leaf_node), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess && summary->n_listed) {
+        e = hipMemcpyAsync(problems, d_list, summary->n_listed * sizeof(pcs_leaf_problem), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+    }
+    (void)pcs::scratch_release(id, s);
+    if (e != hipSuccess) (void)hipStreamSynchronize(s);  // nothing of this call left in flight
+    if (e == hipSuccess) summary->n_listed = std::min(summary->n_problems, problem_cap);
+    return finish(e, "leaf check");
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -2649,6 +2719,46 @@ int pcs_tree_check_host(const void* pages, uint64_t page_size, uint64_t n_pages,
     if (int rc = require_device()) return rc;
     return host_tree_check(pages, page_size, n_pages, fp_first, cls, table, table_size, roots, n_roots, nodes, summary,
                            problems, problem_cap);
+}
+
+int pcs_leaf_check_dev(const void* d_pages, uint64_t page_size, uint64_t n_pages, uint64_t fp_first,
+                       const uint8_t* d_class, const uint64_t* d_table, uint64_t table_size,
+                       const pcs_tree_node* d_tree_nodes, pcs_leaf_node* d_leaves, pcs_leaf_summary* d_summary,
+                       pcs_leaf_problem* d_problems, uint64_t problem_cap, pcs_stream_t stream) {
+    static_assert(sizeof(pcs_leaf_node) == 16, "pcs_leaf_node is 16 bytes");
+    static_assert(sizeof(pcs_leaf_problem) == 16, "pcs_leaf_problem is 16 bytes");
+    static_assert(sizeof(pcs_leaf_summary) == 32 * sizeof(uint64_t), "pcs_leaf_summary is 32 x u64");
+    if (const char* why = pcs::leaf_args(d_pages, page_size, n_pages, fp_first, d_table, table_size, d_summary,
+                                         d_problems, problem_cap))
+        return fail(PCS_ERR_INVALID, why);
+    if (n_pages && !d_class) return fail(PCS_ERR_INVALID, "class bytes are null");
+    if (table_size && !d_tree_nodes) return fail(PCS_ERR_INVALID, "the tree check's nodes are null");
+    if (reinterpret_cast<uintptr_t>(d_table) % 8 || reinterpret_cast<uintptr_t>(d_tree_nodes) % 8 ||
+        reinterpret_cast<uintptr_t>(d_leaves) % 8 || reinterpret_cast<uintptr_t>(d_summary) % 8 ||
+        reinterpret_cast<uintptr_t>(d_problems) % 8)
+        return fail(PCS_ERR_INVALID, "d_table, d_tree_nodes, d_leaves, d_summary or d_problems is misaligned");
+    if (int rc = require_device()) return rc;
+    return finish(pcs::run_leaf_check(static_cast<const uint8_t*>(d_pages), page_size, n_pages, fp_first, d_class,
+                                      d_table, table_size, reinterpret_cast<const uint64_t*>(d_tree_nodes),
+                                      reinterpret_cast<uint64_t*>(d_leaves), reinterpret_cast<uint64_t*>(d_summary),
+                                      reinterpret_cast<uint64_t*>(d_problems), problem_cap,
+                                      reinterpret_cast<hipStream_t>(stream)),
+                  "leaf check kernel launch");
+}
+
+int pcs_leaf_check_host(const void* pages, uint64_t page_size, uint64_t n_pages, uint64_t fp_first, const uint8_t* cls,
+                        const uint64_t* table, uint64_t table_size, const uint64_t* roots, uint32_t n_roots,
+                        pcs_tree_node* tree_nodes, pcs_tree_summary* tree_summary, pcs_leaf_node* leaves,
+                        pcs_leaf_summary* summary, pcs_leaf_problem* problems, uint64_t problem_cap) {
+    if (const char* why = pcs::tree_args(pages, page_size, n_pages, fp_first, table, table_size, roots, n_roots,
+                                         summary, problems, problem_cap))
+        return fail(PCS_ERR_INVALID, why);
+    if (!cls && n_pages && page_size < 249)
+        return fail(PCS_ERR_INVALID, "page_size must be >= 249 to scrub the pages (cls is null)");
+    if (injected_failure()) return fail(PCS_ERR_HIP, "injected failure (PCS_TUNE_FAIL_INJECT)");
+    if (int rc = require_device()) return rc;
+    return host_leaf_check(pages, page_size, n_pages, fp_first, cls, table, table_size, roots, n_roots, tree_nodes,
+                           tree_summary, leaves, summary, problems, problem_cap);
 }
 
 int pcs_shard_range(uint64_t n, int world, int rank, uint64_t* begin, uint64_t* end) {

@@ -33,6 +33,7 @@
 #include <stdint.h>
 
 #include "eloqstore_pcs_internal.h"
+#include "page_stage.h"
 #include "tree_check.h"
 
 namespace pcs {
@@ -178,23 +179,7 @@ __global__ __launch_bounds__(256) void k_tree_level(uint32_t depth, const uint8_
         }
         const uint8_t* src = pg;
         if (staged) {
-            if (decode) {
-                // page byte j goes to lds[off + j], off = the page's address mod 16: whole aligned
-                // 16-byte chunks inside the page move as one load, its head and tail bytewise
-                const uint32_t off = (uint32_t)(reinterpret_cast<uintptr_t>(pg) & 15);
-                uint8_t* dst = lds[w] + off;
-                const uint32_t head = min(P, (16u - off) & 15u);
-                const uint32_t chunks = (P - head) / 16;
-                for (uint32_t q = lane; q < chunks; q += 64)
-                    *reinterpret_cast<u32x4*>(dst + head + 16 * q) =
-                        *reinterpret_cast<const u32x4*>(pg + head + 16 * q);
-                const uint32_t tail0 = head + 16 * chunks;
-                for (uint32_t j = lane; j < head + (P - tail0); j += 64) {
-                    const uint32_t b = j < head ? j : tail0 + (j - head);
-                    dst[b] = pg[b];
-                }
-                src = dst;
-            }
+            if (decode) src = stage_page_lds(pg, P, lane, lds[w]);
             __syncthreads();
         }
         uint64_t n_children = 0, n_bad = 0;

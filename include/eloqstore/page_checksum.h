@@ -324,6 +324,42 @@ TreeReport CheckTree(std::span<const uint8_t> pages, size_t page_size, uint64_t 
                      std::span<const uint8_t> classes, std::span<const uint64_t> table,
                      std::span<const uint64_t> roots, size_t max_listed = 1024);
 
+// Leaf check (pcs_leaf_check_host): the tree check as above, and then every data
+// page it reached in good health is decoded entry by entry and the overflow
+// chain of every large value is walked.  tree is the tree check's report (its
+// problems list every reached page with a bit set, uncapped); leaves[p]
+// describes table row p (owner UINT32_MAX: neither a checked data page nor an
+// overflow page some value claimed); problems lists the checked or claimed
+// rows with any bit set, ascending by page id, at most max_listed of them;
+// n_problems is always full.  The bits are enum pcs_leaf_bits of eloqstore_pcs.h.
+struct LeafNode {
+    uint32_t owner = UINT32_MAX;
+    uint16_t owner_entry = 0, bits = 0;
+    uint32_t a = 0, b = 0;
+};
+struct LeafProblem {
+    uint32_t page_id = 0, owner = 0, bits = 0, owner_entry = 0;
+};
+struct LeafReport {
+    TreeReport tree;
+    uint64_t n_pages = 0, table_size = 0, n_data_pages = 0, n_data_ok = 0;
+    uint64_t n_entries = 0, n_overflow_values = 0, n_expiring = 0, n_compressed = 0;
+    uint64_t inline_value_bytes = 0, overflow_value_bytes = 0;
+    uint64_t n_refs = 0, n_out_of_range_refs = 0, n_extra_refs = 0, n_refs_to_tree = 0;
+    uint64_t n_misplaced_pointers = 0, n_chain_capped = 0, max_groups = 0, n_overflow_pages = 0;
+    uint64_t n_by_bit[9] = {};
+    uint64_t n_problems = 0, first_problem = UINT64_MAX;
+    uint64_t n_leaked_overflow = 0, n_overflow_ok = 0;
+    std::vector<LeafProblem> problems;
+    std::vector<LeafNode> leaves;
+};
+int TryCheckLeaves(std::span<const uint8_t> pages, size_t page_size, uint64_t fp_first,
+                   std::span<const uint8_t> classes, std::span<const uint64_t> table, std::span<const uint64_t> roots,
+                   LeafReport& report, size_t max_listed = 1024);
+LeafReport CheckLeaves(std::span<const uint8_t> pages, size_t page_size, uint64_t fp_first,
+                       std::span<const uint8_t> classes, std::span<const uint64_t> table,
+                       std::span<const uint64_t> roots, size_t max_listed = 1024);
+
 // Registers a page-pool chunk or io_uring buffer ring once (PagesPool::Extend,
 // src/storage/page.cpp:95-120): batches whose pages all lie in registered
 // memory are then hashed in place over PCIe in one launch, with no gather

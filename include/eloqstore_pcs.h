@@ -111,7 +111,9 @@ enum pcs_flags {
  *      pcs_live_summary; PCS_TUNE_REPLAY_TILE; pcs_tree_check_dev /
  *      pcs_tree_check_host, enum pcs_tree_bits, struct pcs_tree_node,
  *      pcs_tree_problem and pcs_tree_summary, PCS_TREE_MAX_DEPTH and
- *      PCS_TREE_CLASS_ABSENT */
+ *      PCS_TREE_CLASS_ABSENT; pcs_leaf_check_dev / pcs_leaf_check_host, enum
+ *      pcs_leaf_bits, struct pcs_leaf_node, pcs_leaf_problem and
+ *      pcs_leaf_summary, PCS_LEAF_MAX_GROUPS */
 #define PCS_ABI_VERSION 7
 int pcs_abi_version(void);
 const char *pcs_version(void);
@@ -787,9 +789,10 @@ int pcs_scrub_live_host(const uint8_t *cls, uint64_t n_pages, uint64_t fp_first,
  * from call to call (claims by atomicMin, the list by ordered compaction).
  * unreached_by_type counts the mapped rows no root reaches whose page is in the
  * window with class byte 1, by the scrub's six type buckets; overflow pages hang
- * off data-page entries, which are not decoded, so bucket 3 is expected to be
- * non-zero, while an unreached mapped index or data page is a leak or a lost
- * subtree.
+ * off data-page entries, which this call does not decode, so bucket 3 is
+ * non-zero for any store with large values: the leaf check (below) walks them
+ * and says which of them no value claims (n_leaked_overflow).  An unreached
+ * mapped index or data page is a leak or a lost subtree.
  *
  * Limits (PCS_ERR_INVALID): 32 <= page_size <= 65535, table_size <= 2^32 - 1,
  * 1 <= n_roots <= 8; n_pages == 0 and table_size == 0 are legal.  d_table,
@@ -849,6 +852,146 @@ int pcs_tree_check_host(const void *pages, uint64_t page_size, uint64_t n_pages,
                         const uint8_t *cls /* may be NULL */, const uint64_t *table, uint64_t table_size,
                         const uint64_t *roots, uint32_t n_roots, pcs_tree_node *nodes /* may be NULL */,
                         pcs_tree_summary *summary, pcs_tree_problem *problems, uint64_t problem_cap);
+
+/* ---- leaf check: decode data pages and follow overflow chains -----------------
+ * The last layer of the offline check.  The tree check stops at the data pages;
+ * every call a reader makes after the index descent goes through DataPageIter
+ * and, for large values, GetOverflowValue.  The leaf check decodes every data
+ * page the tree reached in good health and walks the overflow chain of every
+ * large value.  It reuses what the tree check produced: d_pages, d_class,
+ * d_table and the window follow the tree check's conventions and limits, and
+ * d_tree_nodes is the node array of a tree check over the same inputs
+ * (required; it is only read).
+ *
+ * Page rules, little-endian (DataPageBuilder, src/storage/
+ * data_page_builder.cpp:129-236; DataPageIter, src/storage/data_page.cpp:
+ * 337-469; OverflowPage, data_page.cpp:518-609).  A data page has type byte 2,
+ * content length C = LE16 @9 with 21 <= C <= page_size, prev and next at 11 and
+ * 15, R = LE16 @(C - 2) restart offsets o[k] = LE16 @(E + 2k) from E = C - 2 (1
+ * + R) >= 19.  R == 0 requires E == 19; R == 1 with o[0] == E == 19 is the
+ * builder's empty page; otherwise o[0] == 19, o[k] < o[k + 1], o[R - 1] < E, and
+ * every region [o[k], o[k + 1]) (o[R] = E) is a whole number of entries
+ *   varint32 shared | varint32 non_shared | varint32 stored_len | non_shared
+ *   key bytes | stored_len >> 4 value bytes | [varint64 expire_ts iff
+ *   stored_len & 2] | varint64 timestamp delta
+ * every varint inside the region (a varint32 at most 5 bytes, a varint64 at
+ * most 10), shared == 0 in a region's first entry and <= the previous key
+ * length otherwise, non_shared + value_len within the rest of the region, the
+ * compression bits (stored_len >> 2 & 3) not 3, and for an overflow entry
+ * (stored_len & 1) value_len % 4 == 0 and 4 <= value_len <= 512: its value
+ * bytes are value_len / 4 LE32 logical page ids.  This is stricter than the
+ * reference's iterator (which bounds an entry by the end of the entries, not by
+ * its region) and yields the same entries on every page the builder writes.  A
+ * page that breaks any rule is MALFORMED and yields no entry and no pointer; no
+ * byte outside the page is read.  Key order is not checked (the comparator is
+ * pluggable: include/comparator.h), values are not decompressed.  An overflow
+ * page has type byte 3, V = LE16 @9 value bytes from offset 11, n = byte
+ * (page_size - 1) pointers as LE32 ending at page_size - 1; the intrinsic rule
+ * is n <= 128 and 11 + V + 4 n + 1 <= page_size.  Whether a page that is not
+ * the last of its group is full is not checked: that depends on
+ * KvOptions::overflow_pointers, which no file records.
+ *
+ * Data pages: row p is checked iff the tree reached it as a data page with none
+ * of the six bits UNMAPPED .. MALFORMED.  Its node has owner = p, a = its
+ * entries and b = its overflow values (both 0 when MALFORMED).
+ *
+ * Overflow chains (GetOverflowValue, src/tasks/task.cpp:117-155): for every
+ * overflow entry of a well-formed page the chain is walked group by group, the
+ * entry's pointers being the first group and the pointers of a group's LAST
+ * page the next.  The entry's key is (data page id << 32 | entry byte offset <<
+ * 16).  Every pointer c of a group is counted in n_refs and takes the first of
+ *   c >= table_size          n_out_of_range_refs, BAD_POINTER on the data page
+ *   the tree reached c       n_refs_to_tree, BAD_CHAIN on the data page; c is
+ *                            not claimed
+ *   otherwise                c is claimed: its owner is the smallest key that
+ *                            names it, `a` counts the pointers to it (mod 2^32),
+ *                            and it gets the first that applies of UNMAPPED,
+ *                            ABSENT, BLANK, CORRUPT (as in the tree check),
+ *                            WRONG_TYPE (type byte != 3) and MALFORMED (the
+ *                            intrinsic rule); any of them sets BAD_CHAIN on the
+ *                            data page.  A page with none of them that is not
+ *                            the last of its group and has n != 0 is counted in
+ *                            n_misplaced_pointers and sets BAD_CHAIN.
+ * The walk goes on iff the group's last pointer was claimed, its page has none
+ * of the six bits and n > 0.  After PCS_LEAF_MAX_GROUPS groups a walk that
+ * would go on stops: the value is counted in n_chain_capped and sets BAD_CHAIN
+ * (a cycle ends there).  Whether a walk goes on depends on pages, table and
+ * class bytes only, never on who won a claim, so every owner is the minimum
+ * over the same bids and every counter the same integer sum on every call.  A
+ * claimed row named by more than one pointer gets SHARED.  Counters that follow
+ * pointers (n_refs, n_misplaced_pointers, ...) count every visit.
+ *
+ * d_leaves[p] (one per table row, may be NULL) describes row p; a row that is
+ * neither a checked data page nor claimed has owner UINT32_MAX and zeros
+ * elsewhere.  d_problems[0 .. n_listed) are the checked or claimed rows with
+ * bits != 0 in ascending page_id, capped at problem_cap (may be NULL iff
+ * problem_cap == 0); entries at n_listed and beyond are not written.  n_by_bit
+ * counts those rows by bit.  n_leaked_overflow counts the rows that are mapped,
+ * in the window, of class 1 and type 3, that no value claimed and the tree did
+ * not reach: the overflow pages the tree check could say nothing about.
+ *
+ * Limits and alignment are the tree check's (d_tree_nodes and d_leaves 8-byte
+ * aligned).  The _dev form never synchronises: five launches of fixed size, no
+ * count read back; its scratch is event-fenced per stream (at most 28 bytes per
+ * table row).  One wavefront decodes one data page and walks its chains, so a
+ * page full of values that each run into the group cap keeps one wavefront busy
+ * for 4096 dependent loads per value.
+ *
+ * pcs_leaf_check_host takes host pointers as pcs_tree_check_host does, scrubs
+ * the pages on the device when cls == NULL (page_size >= 249 then), runs the
+ * tree check and then the leaf check there, and returns both summaries
+ * (tree_summary may be NULL; its n_listed is 0, the tree's problems being
+ * exactly its reached nodes with bits != 0), optionally both node arrays, and
+ * the leaf problems.  PCS_TUNE_FAIL_INJECT applies to it. */
+#define PCS_LEAF_MAX_GROUPS 4096
+enum pcs_leaf_bits { /* the low six are pcs_tree_bits' UNMAPPED .. MALFORMED */
+    PCS_LEAF_BAD_POINTER = 64, PCS_LEAF_BAD_CHAIN = 128, PCS_LEAF_SHARED = 256,
+};
+typedef struct pcs_leaf_node { /* 16 bytes, one per table row */
+    uint32_t owner;        /* data page checked: its own id; overflow row claimed: the data page of its smallest
+                              bidder; else UINT32_MAX */
+    uint16_t owner_entry;  /* byte offset of that entry in the owner; 0 for a data page */
+    uint16_t bits;         /* pcs_leaf_bits */
+    uint32_t a;            /* data page: entries;         overflow row: references */
+    uint32_t b;            /* data page: overflow values; overflow row: V | n << 16 (0 unless the page has none of
+                              the six bits) */
+} pcs_leaf_node;
+typedef struct pcs_leaf_problem { /* checked or claimed rows with bits != 0, ascending page_id, capped */
+    uint32_t page_id, owner, bits, owner_entry;
+} pcs_leaf_problem;
+typedef struct pcs_leaf_summary { /* 32 x u64, the same layout on device and host */
+    uint64_t n_pages, table_size;
+    uint64_t n_data_pages;          /* rows checked */
+    uint64_t n_data_ok;             /* of them with bits == 0 */
+    uint64_t n_entries, n_overflow_values, n_expiring, n_compressed; /* over the well-formed data pages */
+    uint64_t inline_value_bytes;    /* value bytes of the entries that do not overflow */
+    uint64_t overflow_value_bytes;  /* V summed once per claimed row with none of the six bits */
+    uint64_t n_refs;                /* pointers followed, the entries' own included */
+    uint64_t n_out_of_range_refs;
+    uint64_t n_extra_refs;          /* pointers to a claimed row beyond the first */
+    uint64_t n_refs_to_tree;
+    uint64_t n_misplaced_pointers;
+    uint64_t n_chain_capped;
+    uint64_t max_groups;            /* the longest walk, in groups */
+    uint64_t n_overflow_pages;      /* claimed rows */
+    uint64_t n_by_bit[9];           /* checked or claimed rows with bit 1 << k set */
+    uint64_t n_problems;
+    uint64_t first_problem;         /* smallest page_id with bits != 0, UINT64_MAX when none */
+    uint64_t n_listed;              /* min(n_problems, problem_cap) */
+    uint64_t n_leaked_overflow;     /* mapped, in the window, class 1, type 3, neither claimed here nor reached by
+                                       the tree */
+    uint64_t n_overflow_ok;         /* claimed rows with bits == 0 */
+} pcs_leaf_summary;
+int pcs_leaf_check_dev(const void *d_pages, uint64_t page_size, uint64_t n_pages, uint64_t fp_first,
+                       const uint8_t *d_class, const uint64_t *d_table, uint64_t table_size,
+                       const pcs_tree_node *d_tree_nodes /* required: a tree check's output over the same inputs */,
+                       pcs_leaf_node *d_leaves /* may be NULL */, pcs_leaf_summary *d_summary,
+                       pcs_leaf_problem *d_problems, uint64_t problem_cap, pcs_stream_t stream);
+int pcs_leaf_check_host(const void *pages, uint64_t page_size, uint64_t n_pages, uint64_t fp_first,
+                        const uint8_t *cls /* may be NULL */, const uint64_t *table, uint64_t table_size,
+                        const uint64_t *roots, uint32_t n_roots, pcs_tree_node *tree_nodes /* may be NULL */,
+                        pcs_tree_summary *tree_summary /* may be NULL */, pcs_leaf_node *leaves /* may be NULL */,
+                        pcs_leaf_summary *summary, pcs_leaf_problem *problems, uint64_t problem_cap);
 
 /* ---- sharding ------------------------------------------------------------
  * Contiguous page range [begin, end) of rank `rank` of `world` for n pages:

@@ -76,6 +76,20 @@
 //       blank; else 0.  ABSENT (nothing was checked) and BAD_LINK (no store
 //       written by the reference was at hand to confirm that every committed
 //       state keeps the sibling links) are printed and never change the status.
+//   page_checksum_tool --leaves <manifest> <page_size> <pages_per_file_shift> <data_file>...
+//       can every value be read back?  Everything --tree does and prints
+//       (pcs_leaf_check_host runs the tree check first), then every data page
+//       the tree reached in good health is decoded and the overflow chain of
+//       every large value walked: two summary lines (data pages and entries;
+//       overflow pages, pointers and leaked pages) and one line per problem
+//       (page id, owner, the owner's entry offset, bit names).  Exit 2 when a
+//       row is unmapped, corrupt, of the wrong type, malformed or has a bad
+//       pointer, or when a chain points into the tree, has pointers in a page
+//       that is not the last of its group or was cut at the group cap, or when
+//       --tree would exit 2; else 3 when a chain page is blank; else as --tree.
+//       ABSENT, SHARED and leaked overflow pages are printed and never change
+//       the status: no store written by the reference was at hand to confirm
+//       that every committed state is free of them.
 //   --scan/--stamp print a summary line with the GiB/s of the call; exit codes
 //   as above (--scan: 2 if any page is corrupted).
 #include <fcntl.h>
@@ -97,6 +111,7 @@
 #include "eloqstore_pcs.h"
 #include "extent_merge.h"
 #include "file_merge.h"
+#include "leaf_check.h"
 #include "manifest_replay.h"
 #include "manifest_scan.h"
 #include "scrub_merge.h"
@@ -138,8 +153,14 @@ void usage(const char* prog) {
                  "           walks the index tree from root and ttl_root; exit 2: a reached page is corrupt,\n"
                  "           malformed, of the wrong type, unmapped or points beyond the table; exit 3: a reached\n"
                  "           page is blank.  absent pages (files not given) and bad-link (sibling links: not\n"
-                 "           confirmed against a store written by the reference) are printed, never fail the run\n",
-                 prog, prog, prog, prog, prog, prog, prog, prog, prog);
+                 "           confirmed against a store written by the reference) are printed, never fail the run\n"
+                 "       %s --leaves <manifest_file> <page_size_bytes> <pages_per_file_shift> <data_file>...\n"
+                 "           --tree, then every reached data page is decoded and every overflow chain walked;\n"
+                 "           exit 2: a data page is malformed, a chain page is unmapped, corrupt, of the wrong type or\n"
+                 "           malformed, a pointer leaves the table or enters the tree, a page that is not the last of\n"
+                 "           its group has pointers, or a chain exceeds 4096 groups; exit 3: a chain page is blank;\n"
+                 "           else as --tree.  absent, shared and leaked overflow pages are printed, never fail the run\n",
+                 prog, prog, prog, prog, prog, prog, prog, prog, prog, prog);
 }
 
 constexpr uint64_t kDefaultPageSize = 4096;  // KvOptions{}.data_page_size
@@ -840,8 +861,9 @@ int live(const char* manifest, const char* size_s, const char* shift_s, int n_fi
 }
 
 // --tree: replay the manifest, load the given data files into one window,
-// scrub them and walk the index tree from root and ttl_root.
-int tree(const char* manifest, const char* size_s, const char* shift_s, int n_files, char** files) {
+// scrub them and walk the index tree from root and ttl_root.  --leaves: the
+// same, and then the data pages are decoded and the overflow chains walked.
+int tree(bool with_leaves, const char* manifest, const char* size_s, const char* shift_s, int n_files, char** files) {
     uint64_t page_size = 0, shift = 0;
     if (!parse_u64(size_s, page_size) || page_size == 0 || !parse_u64(shift_s, shift) || shift > 40) {
         std::fprintf(stderr, "Invalid page size or pages_per_file_shift\n");
@@ -891,14 +913,29 @@ int tree(const char* manifest, const char* size_s, const char* shift_s, int n_fi
     std::vector<pcs_tree_node> nodes(table.size());
     std::vector<pcs_tree_problem> problems(table.size());
     pcs_tree_summary sum{};
-    const int rc = pcs_tree_check_host(window.data(), page_size, n_pages, fp_first, cls.data(), table.data(), table.size(),
-                                       roots, 2, nodes.data(), &sum, problems.data(), problems.size());
+    std::vector<pcs_leaf_node> leaves(with_leaves ? table.size() : 0);
+    std::vector<pcs_leaf_problem> leaf_problems(with_leaves ? table.size() : 0);
+    pcs_leaf_summary lsum{};
+    int rc;
+    if (with_leaves) {
+        rc = pcs_leaf_check_host(window.data(), page_size, n_pages, fp_first, cls.data(), table.data(), table.size(),
+                                 roots, 2, nodes.data(), &sum, leaves.data(), &lsum, leaf_problems.data(),
+                                 leaf_problems.size());
+        // the tree's problems are its reached nodes with any bit set, ascending
+        sum.n_listed = 0;
+        for (size_t p = 0; rc == PCS_OK && p < nodes.size(); ++p)
+            if (nodes[p].parent != UINT32_MAX && nodes[p].bits)
+                problems[sum.n_listed++] = pcs_tree_problem{(uint32_t)p, nodes[p].parent, nodes[p].bits, nodes[p].depth};
+    } else {
+        rc = pcs_tree_check_host(window.data(), page_size, n_pages, fp_first, cls.data(), table.data(), table.size(),
+                                 roots, 2, nodes.data(), &sum, problems.data(), problems.size());
+    }
     if (rc == PCS_ERR_NOMEM) {
         std::fputs(too_large, stderr);
         return 1;
     }
     if (rc) {
-        std::fprintf(stderr, "Tree check failed (%d): %s\n", rc, pcs_last_error());
+        std::fprintf(stderr, "%s check failed (%d): %s\n", with_leaves ? "Leaf" : "Tree", rc, pcs_last_error());
         return 1;
     }
     static const char* const tree_name[2] = {"root", "ttl_root"};
@@ -932,16 +969,34 @@ int tree(const char* manifest, const char* size_s, const char* shift_s, int n_fi
                 (unsigned long long)sum.unreached_by_type[1], (unsigned long long)sum.unreached_by_type[2],
                 (unsigned long long)sum.unreached_by_type[3], (unsigned long long)sum.unreached_by_type[4],
                 (unsigned long long)sum.unreached_by_type[5], (unsigned long long)sum.n_unreached_unread);
-    return pcs::tree_tool_exit(sum);
+    if (!with_leaves) return pcs::tree_tool_exit(sum);
+    using ull = unsigned long long;
+    std::printf("leaves data_pages %llu ok %llu entries %llu overflow_values %llu expiring %llu compressed %llu "
+                "inline_bytes %llu\n",
+                (ull)lsum.n_data_pages, (ull)lsum.n_data_ok, (ull)lsum.n_entries, (ull)lsum.n_overflow_values,
+                (ull)lsum.n_expiring, (ull)lsum.n_compressed, (ull)lsum.inline_value_bytes);
+    std::printf("overflow pages %llu ok %llu value_bytes %llu refs %llu extra %llu out_of_range %llu to_tree %llu "
+                "misplaced %llu capped %llu max_groups %llu leaked %llu\n",
+                (ull)lsum.n_overflow_pages, (ull)lsum.n_overflow_ok, (ull)lsum.overflow_value_bytes, (ull)lsum.n_refs,
+                (ull)lsum.n_extra_refs, (ull)lsum.n_out_of_range_refs, (ull)lsum.n_refs_to_tree,
+                (ull)lsum.n_misplaced_pointers, (ull)lsum.n_chain_capped, (ull)lsum.max_groups,
+                (ull)lsum.n_leaked_overflow);
+    for (uint64_t k = 0; k < lsum.n_listed; ++k) {
+        char names[112];
+        pcs::leaf_bit_names(leaf_problems[k].bits, names);
+        std::printf("  leaf problem: page_id %u owner %u entry %u %s\n", leaf_problems[k].page_id, leaf_problems[k].owner,
+                    leaf_problems[k].owner_entry, names);
+    }
+    return pcs::leaf_tool_exit(lsum, pcs::tree_tool_exit(sum));
 }
 
 int main(int argc, char** argv) {
-    if (argc >= 2 && !std::strcmp(argv[1], "--tree")) {
+    if (argc >= 2 && (!std::strcmp(argv[1], "--tree") || !std::strcmp(argv[1], "--leaves"))) {
         if (argc < 6) {
             usage(argv[0]);
             return 1;
         }
-        return tree(argv[2], argv[3], argv[4], argc - 5, argv + 5);
+        return tree(argv[1][2] == 'l', argv[2], argv[3], argv[4], argc - 5, argv + 5);
     }
     if (argc >= 2 && !std::strcmp(argv[1], "--live")) {
         if (argc < 6) {
